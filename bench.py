@@ -15,10 +15,21 @@ mesh; weak scaling.  The data-path exchange (interface DoF sum, Krylov scalars) 
 library over RCCL when it is built with the partitioned solver; torch.distributed (gloo) only
 carries the barrier, the id broadcast and the max-over-ranks timing.
 
-Extra fields on the JSON line: roofline (dominant kernel = fused PA apply, HIP events at its dispatch
-start / end on the library stream, in a profiled pass of the same steps right after the uninstrumented
-timed region), cpu_baseline (the oracle's FA-CSR + Jacobi-CG restatement of
-the reference CPU path, timed on this host, rank 0 at N=1 only).
+A plain run sets up, warms up, times the --steps steps and prints the result line (metric, value,
+unit, higher_is_better, dtype, ms_per_step, config); roofline and cpu_baseline are null on it.
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned is written as float64
+DIR/x.npy (the solution vector; N>1: x_rank<r>.npy per rank) and DIR/solve_info.npy (iterations,
+final and initial residual norm).  A vector too long for the 64 MB budget is written as a fixed,
+seeded sample: x.npy holds the sampled entries and x_index.npy their positions.  The inputs are
+seeded, so two runs with the same arguments solve the same system.
+
+--full adds the legs that take runs of their own, after the timed region: roofline (dominant kernel
+= fused PA apply, HIP events at its dispatch start / end on the library stream, in a profiled pass of
+the same steps), cpu_baseline (the oracle's FA-CSR + Jacobi-CG restatement of the reference CPU path,
+timed on this host, rank 0 at N=1 only), and the informational kronecker_form, gmres, spd_cg,
+per_point_qdata and host_boundary_rate lines.  The --no-* / --*-steps switches below trim those legs
+and mean something only with --full.
 """
 import argparse
 import json
@@ -47,6 +58,11 @@ def parse():
     ap.add_argument("--order", type=int, default=None, help="default 2 (c2) / 4 (c3)")
     ap.add_argument("--cg-iters", type=int, default=None, help="default 100 (c2) / 20 (c3)")
     ap.add_argument("--kinds", type=int, default=7, help="1 diffusion | 2 convection | 4 mass")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline pass, the CPU baseline and the informational "
+                         "legs (kronecker_form, gmres, spd_cg, per_point_qdata, host_boundary_rate)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--spd-steps", type=int, default=2,
                     help="informational CG line on the symmetric kK+sM operator (steps of 200 it); 0 = skip")
@@ -398,6 +414,26 @@ def _cpu_baseline_kuhn(args, O, n, p, threads, host, mesh=None):
             **rec, **host_bw, **host}
 
 
+DUMP_BUDGET = 48 << 20  # bytes of x over all ranks (the 64 MB limit less the index and info files)
+
+
+def dump_outputs(args, ctx, dX, nl, info, rank=0, world=1):
+    """--dump-outputs: the solution vector the last timed step left in dX and that step's solver
+    record.  A vector over the budget is sampled at fixed, seeded positions (sorted, with repeats
+    removed), which are written beside it."""
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    x = ctx.from_device(dX, nl)
+    cap = DUMP_BUDGET // 8 // world
+    if nl > cap:
+        idx = np.unique(np.random.default_rng(20261019 + rank).integers(0, nl, cap // 2))
+        np.save(os.path.join(args.dump_outputs, f"x_index{tag}.npy"), idx.astype(np.float64))
+        x = x[idx]
+    np.save(os.path.join(args.dump_outputs, f"x{tag}.npy"), np.ascontiguousarray(x, dtype=np.float64))
+    np.save(os.path.join(args.dump_outputs, f"solve_info{tag}.npy"),
+            np.array([info["iterations"], info["final_norm"], info["initial_norm"]], dtype=np.float64))
+
+
 def main_c4(args):
     """BASELINE configs[3]: unstructured-path tets, FA CSR SpMV + GMRES(30)/Jacobi on 1 GPU."""
     import cdfem
@@ -441,12 +477,16 @@ def main_c4(args):
     # timed region: the production path, no instrumentation
     t0 = time.perf_counter()
     iters = 0
+    info = None
     for _ in range(args.steps):
-        iters += step()["iterations"]
+        info = step()
+        iters += info["iterations"]
     ctx.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and info is not None:
+        dump_outputs(args, ctx, dX, mesh.nl, info)
     roof = None
-    if not args.no_profile_events:
+    if args.full and not args.no_profile_events:
         # profiled pass of the same steps: HIP events around the SpMV (dispatch start / end) and the
         # orthogonalisation.  Events carry completion fences, so they stay out of the timed region.
         ctx.set_option("profile_mask", (1 << cdfem.K_APPLY) | (1 << cdfem.K_ORTH))
@@ -482,7 +522,7 @@ def main_c4(args):
         roof["survey_bytes_per_launch"] = sb
         roof["survey_frac"] = round(sb / (roof["avg_launch_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline_c4(args, n, p, mesh if unstructured else None)
         except Exception as e:
@@ -603,6 +643,7 @@ def main():
     ctx.synchronize()
     t0 = time.perf_counter()
     iters = 0
+    info = None
     for _ in range(args.steps):
         info = step()
         iters += info["iterations"]
@@ -610,6 +651,8 @@ def main():
     barrier(pg)
     dt = time.perf_counter() - t0
     dt_max = allmax(pg, dt)
+    if args.dump_outputs and info is not None:
+        dump_outputs(args, ctx, dX, mesh.nl, info, rank, world)
     comm_timing = None
     if host_comm:
         cs = dict(ctx.comm_stats)
@@ -626,7 +669,7 @@ def main():
     # events at the kernel's dispatch start / end on the library stream.  Event-bracketed launches
     # carry completion fences (measured ~8 % of a C2 iteration), so they stay out of the timed region.
     roof = None
-    if not args.no_profile_events:
+    if args.full and not args.no_profile_events:
         ctx.set_option("profile_mask", 1 << cdfem.K_APPLY)
         ctx.profile(True)
         for _ in range(args.steps):
@@ -719,7 +762,7 @@ def main():
     # informational: the same steps with the Kronecker form of the per-element factors (pa_uniform 0,
     # the form any affine box takes), when the uniform element matrix ran above
     kron = None
-    if world == 1 and uniform and not args.no_kron_form:
+    if args.full and world == 1 and uniform and not args.no_kron_form:
         ctx.set_option("pa_uniform", 0)
         step()
         ctx.synchronize()
@@ -733,7 +776,7 @@ def main():
 
     # host-boundary (PCIe-inclusive) rate: one solve with B and X in host memory (not `value`)
     host_rate = None
-    if world == 1:
+    if args.full and world == 1:
         t0 = time.perf_counter()
         _, hinfo = ctx.solve(B, method="cg", pc="jacobi", rel_tol=0.0, abs_tol=0.0,
                              max_iter=args.cg_iters, check_every=args.cg_iters)
@@ -741,7 +784,7 @@ def main():
 
     # informational: GMRES(30) + Jacobi (Input/petsc.opts) on the same operator, fixed inner steps
     gm = None
-    if world == 1 and args.gmres_iters > 0:
+    if args.full and world == 1 and args.gmres_iters > 0:
         def gstep():
             return ctx.solve_device(dB, dX, method="gmres", pc="jacobi", rel_tol=0.0, abs_tol=0.0,
                                     max_iter=args.gmres_iters, restart=30)
@@ -773,7 +816,7 @@ def main():
     # informational: SURVEY §8d's symmetric CG operator kK + sM (c = 0), where CG is a convergent
     # method; fixed 200 iterations per solve, same mesh
     spd = None
-    if world == 1 and args.kinds == 7 and args.spd_steps > 0:
+    if args.full and world == 1 and args.kinds == 7 and args.spd_steps > 0:
         ctx.pa_setup(kinds=5, kappa=0.1, mass=1.0)
         _, B5 = ctx.form_linear_system(np.zeros(mesh.nl), b)
         dB5 = ctx.to_device(B5)
@@ -805,7 +848,7 @@ def main():
     # informational: the same CG steps with MFEM's per-point qdata stream (pa_affine 0), so the line
     # shows both forms of the operator on one box
     per_point = None
-    if world == 1 and affine and args.per_point_steps > 0 and args.config in ("c2", "c3"):
+    if args.full and world == 1 and affine and args.per_point_steps > 0 and args.config in ("c2", "c3"):
         c2 = cdfem.Context(local % ndev)
         for k, v in args.set.items():
             c2.set_option(k, v)
@@ -847,7 +890,7 @@ def main():
     out = None
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 # c5: the 256^3 FA matrix is out of the host's reach; per-DoF rate on the 64^3 mesh
                 cpu = cpu_baseline(args, min(n, 64), p, args.kinds)

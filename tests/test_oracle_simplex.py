@@ -172,7 +172,7 @@ def test_ilu0_gmres_converges_faster_than_jacobi():
     assert np.abs(_ilu_lu(F) @ z - r).max() <= 1e-11 * np.abs(r).max()
 
 
-def test_radial_mms_on_synthetic_disk_converges():
+def test_radial_mms_on_synthetic_disk_converges(tmp_path):
     """Circle variant MMS (linear_convection_diffusion_2D_circle.cpp:140-215) through the oracle on the
     synthetic gmsh disk: the L2 error falls under refinement (P2 on a polygonal domain: the boundary
     approximation limits the rate to about 2) and the forcing matches a finite-difference restatement."""
@@ -184,7 +184,7 @@ def test_radial_mms_on_synthetic_disk_converges():
     from oracle import oracle as O
     errs = []
     for nr in (6, 12):
-        path = f"/tmp/cdfem_disk_{nr}.msh"
+        path = str(tmp_path / f"cdfem_disk_{nr}.msh")
         gmsh_synth.write_circle(path, nr, perturb=0.0)
         m = cdfem.gmsh_mesh(path, 2)
 

@@ -9,8 +9,8 @@ reference's two default configurations:
           (linear_convection_diffusion_2D_circle.cpp:140-215), Input/petsc_circle.opts (GMRES(30) +
           bjacobi/ILU(0), rtol 1e-10, atol 1e-12, max_it 2000); :294-304, 372
 
-CPU: the fixture equals the reference files as the product reader sees them (when /root/reference
-exists), the sizes (938 / 510 / 80 and 3056 / 1593 / 128), and the dof numbering equals an
+CPU: the fixture equals the reference files as the product reader sees them (against the record
+tests/golden/reference_reader_output.npz of the reader on those files), the sizes (938 / 510 / 80 and 3056 / 1593 / 128), and the dof numbering equals an
 independent restatement of MFEM's (Mesh(file, 1, 1) finalize + first-met edge order), which PETSc's
 ILU(0) depends on.
 GPU: both configurations end to end against the oracle (iterations +-1, MMS L2 to 1e-6 relative,
@@ -18,6 +18,7 @@ solutions to 1e-10 relative L2 when both sides solve to rtol 1e-13), through the
 binding and through the MFEM-shaped C++ driver, plus `mpiexec -n 2` of both against one rank.
 Parity is against the oracle (MFEM/PETSc are absent: parity unpinned beyond the oracle).
 """
+import json
 import os
 import subprocess
 import sys
@@ -81,22 +82,23 @@ def _om(m):
 @pytest.mark.parametrize("name", ["square", "circle"])
 def test_fixture_is_the_reference_mesh(msh, name):
     """The product reader gives bitwise the same topology and order-3 space from the fixture's file
-    as from the reference's own file (skipped where /root/reference is absent, e.g. the GPU box)."""
-    ref = R.reference_file(name)
-    if ref is None:
-        pytest.skip("/root/reference not present")
+    as from the reference's own file.  What the reader gave on the reference's file, and the digests
+    of an independent parse of it, are recorded in tests/golden/reference_reader_output.npz
+    (tests/golden/make_reference_reader_output.py), so the test needs nothing outside the repository."""
     sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import make_reference_meshes as MK
-    raw = MK.parse_msh(ref)
-    fx = R.load(name)
-    for k in ("node_id", "node_xyz", "elem_id", "elem_type", "elem_phys", "elem_geom", "elem_nodes"):
-        np.testing.assert_array_equal(fx[k], raw[k])
-    assert fx["physical"] == raw["physical"]
-    for a, b in zip(_topology(ref), _topology(msh[name])):
+    import make_reference_reader_output as MR
+    with np.load(os.path.join(os.path.dirname(R.FIXTURE), "reference_reader_output.npz"), allow_pickle=False) as z:
+        want = {k[len(name) + 1:]: z[k] for k in z.files if k.startswith(name + "_")}
+    assert MR.raw_digests(R.load(name)) == json.loads(str(want["raw_sha256"]))
+    for k, b in zip(("vxyz", "ev", "bv", "ba"), _topology(msh[name])):
+        a = want["topo_" + k]
+        assert a.dtype == b.dtype and a.shape == b.shape
         np.testing.assert_array_equal(a, b)
-    m0, m1 = cdfem.gmsh_mesh(ref, ORDER), cdfem.gmsh_mesh(msh[name], ORDER)
-    for k in ("verts", "dofmap", "ess", "dof_xyz", "bdr_mask"):
-        np.testing.assert_array_equal(getattr(m0, k), getattr(m1, k))
+    m1 = cdfem.gmsh_mesh(msh[name], ORDER)
+    for k in MR.SPACE_KEYS:
+        a, b = want["space_" + k], np.asarray(getattr(m1, k))
+        assert a.dtype == b.dtype and a.shape == b.shape
+        np.testing.assert_array_equal(a, b)
 
 
 @pytest.mark.parametrize("name", ["square", "circle"])

@@ -6,7 +6,7 @@ set -u
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 PATHS=${1:-brick}
-ARGS="--steps 1 --warmup 0 --cg-iters 20 --no-profile-events --no-cpu-baseline"
+ARGS="--full --steps 1 --warmup 0 --cg-iters 20 --no-profile-events --no-cpu-baseline"
 for P in $PATHS; do
   i=0
   for G in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE"; do
