@@ -57,6 +57,35 @@ __device__ __forceinline__ void bstore(__amdgpu_buffer_rsrc_t r, uint32_t off, d
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, v), r, off, 0, 0);
 }
 
+// Patch positions i = t, t + STEP, t + 2 STEP, ... of an S^3 patch (x fastest), advanced incrementally:
+// STEP = dz S^2 + dy S + dx, so each step adds (dx, dy, dz) with carries (a few adds and selects
+// instead of two constant divisions per position; STEP < S^3)
+template <int S, int STEP = 64>
+struct PatchWalk {
+    int x, y, z;
+    __device__ __forceinline__ explicit PatchWalk(unsigned t) : x((int)(t % S)), y((int)((t / S) % S)), z((int)(t / (S * S))) {}
+    __device__ __forceinline__ void next()
+    {
+        constexpr int dx = STEP % S, dy = (STEP / S) % S, dz = STEP / (S * S);
+        x += dx;
+        const int cx = x >= S ? 1 : 0;
+        x -= S & -cx;
+        y += dy + cx;
+        const int cy = y >= S ? 1 : 0;
+        y -= S & -cy;
+        z += dz + cy;
+    }
+};
+
+// v unchanged, but opaque to the optimiser: index arithmetic that depends on it cannot be hoisted
+// above this point (LLVM otherwise computes a later phase's per-position indices at kernel entry
+// and spills them across the element apply)
+__device__ __forceinline__ int opaque(int v)
+{
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
 // The 1-8 patch-buffer entries of lattice dof (gx, gy, gz) summed in a fixed order (lower brick first
 // per face axis, z outermost): eight buffer loads at fixed offsets from its own brick's entry P (the
 // lower brick's face entry along x / y / z sits at P - 1 / P - R / P - A in the pencil layout of
@@ -95,6 +124,11 @@ __device__ __forceinline__ double patch_sum8(__amdgpu_buffer_rsrc_t bp, const Br
     for (int k = 0; k < 8; ++k) q += t[k];
     return q;
 }
+
+// ho_uniform: the 2 x 2 x 4 block CG apply with the dense element matrix (hobrick_um.hip k_hobrick_um), launched
+// by the block CG's launcher in place of k_hobrick_cg when ho_uniform_elem(c)
+hipError_t launch_hobrick_um(cdfem_ctx *c, const BrickGeom &g, const double *r, const double *dinv, const double *d_old,
+                             double *d_new, double *x);
 
 // GMRES on the structured Mult (set_option "gm_pb"): A_c V_j is each row's 1-8 patch entries of the
 // patch-buffer Mult (k_brick3d<..., PBO>), V_j itself on the essential rows; pass 1 forms it there

@@ -46,26 +46,6 @@ __device__ __forceinline__ int brick_id(const BrickGeom &g)
     return (int)(x * q + (x < r ? x : r) + k);
 }
 
-// Patch positions i = t, t + STEP, t + 2 STEP, ... of an S^3 patch (x fastest), advanced incrementally:
-// STEP = dz S^2 + dy S + dx, so each step adds (dx, dy, dz) with carries (a few adds and selects
-// instead of two constant divisions per position; STEP < S^3)
-template <int S, int STEP = 64>
-struct PatchWalk {
-    int x, y, z;
-    __device__ __forceinline__ explicit PatchWalk(unsigned t) : x((int)(t % S)), y((int)((t / S) % S)), z((int)(t / (S * S))) {}
-    __device__ __forceinline__ void next()
-    {
-        constexpr int dx = STEP % S, dy = (STEP / S) % S, dz = STEP / (S * S);
-        x += dx;
-        const int cx = x >= S ? 1 : 0;
-        x -= S & -cx;
-        y += dy + cx;
-        const int cy = y >= S ? 1 : 0;
-        y -= S & -cy;
-        z += dz + cy;
-    }
-};
-
 // PatchWalk plus the lattice index gid = gx + Lx gy + Lxy gz of the position, advanced with the walk's
 // carries (no per-position 32-bit multiplies: v_mul_lo_u32 issues at a quarter of the VALU rate)
 template <int S, int STEP = 64>
@@ -130,15 +110,6 @@ __device__ __forceinline__ void static_for(F &&f)
         f(std::integral_constant<int, B>{});
         static_for<B + 1, E>(f);
     }
-}
-
-// v unchanged, but opaque to the optimiser: index arithmetic that depends on it cannot be hoisted
-// above this point (LLVM otherwise computes a later phase's per-position indices at kernel entry
-// and spills them across the element apply)
-__device__ __forceinline__ int opaque(int v)
-{
-    asm volatile("" : "+v"(v));
-    return v;
 }
 
 // In-LDS E->L schedule.  At P = 2 an element's local dof d lands on patch position 2e + d per axis,
@@ -1399,6 +1370,9 @@ static hipError_t hobrick_launch(cdfem_ctx *c, const double *r, const double *di
     const hipError_t e = ho_ktab(c, &kt);
     if (e != hipSuccess || kt == nullptr) return e != hipSuccess ? e : hipErrorInvalidValue;
     const BrickGeom g = geom_of(c);
+    if constexpr (EZ == 4 && (K == 7 || K == 5)) {  // ho_uniform: the common element matrix on the matrix cores
+        if (ho_uniform_elem(c)) return launch_hobrick_um(c, g, r, dinv, d_old, d_new, x);  // (hobrick_um.hip)
+    }
     const dim3 grid((unsigned)c->hb_nblk), block(NT);
 #define CDFEM_HB(XF_, MF_)                                                                                     \
     CDFEM_LAUNCH(c, (k_hobrick_cg<D1, Q1, K, XF_, MF_, EZ>), grid, block, 0, r, dinv, d_old, d_new, c->d_face, c->d_qaff, \

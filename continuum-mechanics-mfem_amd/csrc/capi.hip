@@ -138,6 +138,7 @@ void free_mesh(cdfem_ctx *c)
     dfree(c->d_sptr); dfree(c->d_srows); dfree(c->d_scols); dfree(c->d_smap); dfree(c->d_sdel); dfree(c->d_svals);
     dfree(c->d_swide);
     dfree(c->d_uelem);
+    dfree(c->d_hoelem);
     c->d_sdel = nullptr;
     c->d_swide = nullptr;
     c->sell_nnz_wide = 0;
@@ -834,6 +835,18 @@ void solve_gmres(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, d
 
 }  // namespace
 
+// ho_uniform: the block CG applies the common element matrix on the matrix cores (k_hobrick_um); the
+// matrix is the PA setup's, for the order and kinds it was formed for, on 2 x 2 x 4 blocks of one rank
+// (shared with hobrick_um.hip and brick_kernels.hip)
+bool cdfem::ho_uniform_path(const cdfem_ctx *c)
+{
+    return c->ho_uniform != 0 && (c->kinds == 7 || c->kinds == 5) && !multi_rank(c) && c->hb_ez == 4 && use_hobrick_cg(c);
+}
+bool cdfem::ho_uniform_elem(const cdfem_ctx *c)
+{
+    return c->d_hoelem != nullptr && c->hoelem_p == c->p && c->hoelem_kinds == c->kinds && ho_uniform_path(c);
+}
+
 // ================================================================================================
 extern "C" {
 
@@ -1413,6 +1426,7 @@ static int pa_setup_form(cdfem_ctx *c, const cdfem_form_coeffs *f)
         c->pa_ready = true;
         c->fa_ready = false;
         c->dinv_ready = false;
+        HIPCHK(setup_ho_uniform_elem(c));  // ho_uniform: the same for the p = 3, 4 block CG (reads the flags above)
         return CDFEM_OK;
     });
 }
@@ -1877,6 +1891,12 @@ int cdfem_set_option(cdfem_ctx *c, const char *key, int value)
         } else if (k == "pa_uniform") {  // the matrix is formed by cdfem_pa_setup; 0 leaves it unused
             if (value != 0 && value != 1) throw ArgError("pa_uniform must be 0 or 1");
             c->pa_uniform = value;
+        } else if (k == "ho_uniform") {  // the matrix is formed by cdfem_pa_setup when 1; 0 leaves it unused
+            if (value != 0 && value != 1) throw ArgError("ho_uniform must be 0 or 1");
+            c->ho_uniform = value;
+        } else if (k == "ho_uniform_grid") {
+            if (value < 0) throw ArgError("ho_uniform_grid must be 0 (automatic) or the number of workgroups");
+            c->ho_uniform_grid = value;
         } else if (k == "brick_mfma") {
             if (value != 0 && value != 1) throw ArgError("brick_mfma must be 0 or 1");
             c->brick_mfma = value;
@@ -2011,6 +2031,7 @@ int cdfem_kernel_name(cdfem_ctx *c, int k, char *buf, size_t n)
         if (k != CDFEM_K_APPLY) throw UnsupportedError("kernel names: the operator apply only");
         const char *name = c->fa_ready ? (c->lds_rows > 0 ? "k_sell_spmv_lds" : "k_sell_spmv")
                            : use_brick(c) ? "k_brick_cg"
+                           : ho_uniform_elem(c) ? "k_hobrick_um"
                            : use_hobrick_cg(c) ? "k_hobrick_cg"
                            : c->qlay == 1 ? (tile_kron(c) ? "k_apply3d_ktile" : "k_apply3d_tile")
                                           : "k_apply3d";
@@ -2035,6 +2056,10 @@ int cdfem_kernel_flops(cdfem_ctx *c, int k, double *flops)
         if (c->qlay == 0 && uniform_elem(c) && use_brick(c)) {
             // the common element matrix (k_brick_cg<..., MX 2>): nd^2 MACs per element (the MFMA tiles'
             // zero padding, 56 x 1024 MACs per 64 elements against 64 x 729, is not counted)
+            *flops = 2.0 * (double)c->nd * c->nd * (double)c->ne;
+            return CDFEM_OK;
+        }
+        if (c->qlay == 1 && ho_uniform_elem(c)) {  // k_hobrick_um: the same count (padding to 128 x 128 not counted)
             *flops = 2.0 * (double)c->nd * c->nd * (double)c->ne;
             return CDFEM_OK;
         }
@@ -2094,7 +2119,10 @@ int cdfem_kernel_bytes(cdfem_ctx *c, int k, double *bytes)
             const double S = brick_patch_side(c), SZ = brick_patch_side_z(c);
             const double patches = 8.0 * S * S * SZ * (double)brick_count(c);
             const bool xf = c->cg_xfold != 0;
-            *bytes = k == CDFEM_K_APPLY ? 8.0 * c->ncomp * ne + 33.0 * nl + patches + (xf ? 16.0 * nl : 0.0)
+            // (ho_uniform: one element matrix in operand order, 16 x 4 padded, instead of the factor stream)
+            const double nrow = 16.0 * ((c->nd + 15) / 16), ncol = 4.0 * ((c->nd + 3) / 4);
+            const double fac = ho_uniform_elem(c) ? 8.0 * nrow * ncol : 8.0 * c->ncomp * ne;
+            *bytes = k == CDFEM_K_APPLY ? fac + 33.0 * nl + patches + (xf ? 16.0 * nl : 0.0)
                                         : (xf ? 25.0 : 49.0) * nl + patches;
             return CDFEM_OK;
         }

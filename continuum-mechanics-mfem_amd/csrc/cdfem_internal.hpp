@@ -178,6 +178,15 @@ struct cdfem_ctx {
                                         // gives), the p = 2 brick CG applies that element's 27 x 27 matrix on
                                         // the matrix cores (k_brick_cg<..., MX 2>); 0 keeps the Kronecker form
     double *d_uelem = nullptr;          // pa_uniform: the common element matrix in MFMA A-operand order
+    int ho_uniform = 0;                 // set_option "ho_uniform": the p = 3, 4 block CG (2 x 2 x 4 blocks) applies the
+                                        // common N x N element matrix of a uniform box (N = 64, 125) as one GEMM on
+                                        // the matrix cores (k_hobrick_um); read by cdfem_pa_setup, 0 afterwards
+                                        // switches back to the Kronecker form without a new setup
+    int ho_uniform_grid = 0;            // set_option "ho_uniform_grid": k_hobrick_um's workgroups (0 automatic; tests)
+    double *d_hoelem = nullptr;         // ho_uniform: that matrix in MFMA A-operand order ([row tile][k step][lane],
+                                        // zero-padded to 16 x 4 multiples: 128 x 128 at p = 4)
+    int hoelem_p = 0;                   //   the order and kinds it was formed for
+    unsigned hoelem_kinds = 0;
     int64_t Lx = 0, Ly = 0, Lz = 0;     // dof lattice per axis
     double *d_face = nullptr;           // [nblk][F] brick-face partial sums
     double *d_ones = nullptr;           // all-ones vector (unpreconditioned brick CG)
@@ -424,6 +433,14 @@ hipError_t launch_update_fin(cdfem_ctx *c, int nparts, int64_t off = 0);
 // that every element's factors equal the first element's (within 1e-14 of the largest) and, if so, forms
 // that element's 27 x 27 matrix (column j = the Kronecker core on e_j) in d_uelem (freed otherwise)
 hipError_t setup_uniform_elem(cdfem_ctx *c);
+// ho_uniform: the same for a structured p = 3, 4 box whose CG runs on 2 x 2 x 4 blocks (kinds 7 or 5, one
+// rank): every element's factors against element 0's, each component within 1e-14 of its own magnitude;
+// if so the 64 x 64 / 125 x 125 element matrix goes to d_hoelem (freed otherwise)
+hipError_t setup_ho_uniform_elem(cdfem_ctx *c);
+// the option is on and the 2 x 2 x 4 block CG of one rank is taken (kinds 7 or 5): the setup's check applies;
+// and the matrix is present too, so the CG apply launches k_hobrick_um
+bool ho_uniform_path(const cdfem_ctx *c);
+bool ho_uniform_elem(const cdfem_ctx *c);
 hipError_t launch_brick_cg2(cdfem_ctx *c, const double *r, const double *dinv, const double *d_old,
                             double *d_new, double *q, double *x = nullptr, int bfkk = -1);
 int cg_den_fold_grid(const cdfem_ctx *c);

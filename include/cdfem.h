@@ -274,6 +274,25 @@ int cdfem_fp64_bench(cdfem_ctx *ctx, int mode, int reps, double *tflops);
  *              CG apply then runs it as a GEMM on the matrix cores (56 v_mfma_f64_16x16x4_f64 per 64
  *              elements; the same operator to rounding).  0 = the Kronecker form (takes effect without a
  *              new setup; 1 needs one).  The GMRES Mult and the other applies keep the Kronecker form.
+ * "ho_uniform": 0 (default) or 1 — the same for the high-order block CG, read by cdfem_pa_setup.  With 1
+ *              the setup checks whether every element's factors equal element 0's, each component within
+ *              1e-14 of its own magnitude, and, if so, forms that element's N x N matrix once (N = 64 at
+ *              p = 3, 125 at p = 4; column j = the Kronecker apply of e_j).  The check is taken when all of
+ *              these hold: a structured 3D box at p = 3 or 4 with the operators' rule (q1 = 5, 6); kinds 7
+ *              or 5; pa_affine 2 on the high-order tile layout; one rank; the block CG ("ho_brick") on
+ *              2 x 2 x 4 blocks ("ho_block_z" 4, whose 16 elements are the 16 columns of one
+ *              v_mfma_f64_16x16x4_f64 tile).  The CG apply is then k_hobrick_um: a persistent kernel whose
+ *              waves each hold a 16-row tile of the matrix in registers and form Y (N x 16) = A X per block
+ *              on the matrix cores (the same operator to rounding; elements of a partial block outside the
+ *              box are masked).  In every other case (not uniform, other kinds, 2^3 blocks, several ranks,
+ *              per-point data) the setup keeps the Kronecker form without a word.  0 after a setup switches
+ *              back without a new setup; 1 needs one.  The GMRES Mult and the other applies keep the
+ *              Kronecker form.  Measured on C3 (profiles/r07/ab_c3_ho_uniform/): level with
+ *              the Kronecker form on the same blocks, 20 % behind the default 2^3 blocks on the apply.
+ * "ho_uniform_grid": 0 (default, automatic: what a CU holds at once, one 8-wave workgroup at p = 4 and two
+ *              of 4 waves at p = 3, times the CUs, at most one workgroup per block) or the number
+ *              of k_hobrick_um workgroups (tests: a small box walked by few workgroups with an uneven
+ *              remainder).  The iterates do not depend on it, bitwise.
  * "brick_mfma": 0 (default) or 1 — the p = 2 brick CG apply's x stage (kinds 7, Kronecker form) on
  *              v_mfma_f64_16x16x4_f64: 16 elements per GEMM, outputs staged through LDS to the element
  *              threads.  Parity-green, measured slower.
