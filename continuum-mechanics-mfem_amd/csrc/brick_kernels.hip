@@ -174,8 +174,6 @@ k_brick3d(const double *__restrict__ x, double *__restrict__ y, double *__restri
     constexpr int S = kBrick * P + 1;
     constexpr int S2 = S * S, S3 = S * S * S;
     constexpr int F = face_count<S>();
-    constexpr int NC = QLayout<K, 3>::nc;
-    constexpr int NQ = Q1 * Q1 * Q1;
     constexpr int NI = (S3 + 63) / 64;
     __shared__ double s_in[S3];
     __shared__ double s_out[S3];
@@ -217,7 +215,7 @@ k_brick3d(const double *__restrict__ x, double *__restrict__ y, double *__restri
     const int o0 = P * ez * S2 + P * ey * S + P * ex;
     double Y[D1][D1][D1];
     auto xl = [&](int dz, int dy, int dx) { return s_in[o0 + dz * S2 + dy * S + dx]; };
-    elem_apply3d_af<D1, Q1, K, AF>(xl, qd + (size_t)b * (AF ? 1 : NQ) * NC * kLanes, t, T, Y);
+    elem_apply3d_af<D1, Q1, K, AF>(xl, qd_block<Q1, K, AF>(qd, b), t, T, Y, qd);
 
     // 3. deterministic E->L inside the brick (brick_e2l: all lanes of a step write distinct targets)
     brick_e2l<D1, S>(s_out, o0, Y);
@@ -445,6 +443,7 @@ static hipError_t brick_launch(cdfem_ctx *c, const double *x, const double *dinv
                                c->d_face, c->d_qaff, c->d_ess, T, g);
         else if (pa_af(c) == 2) CDFEM_B3(2, c->d_qaff);
         else if (pa_af(c) == 1) CDFEM_B3(1, c->d_qaff);
+        else if (pa_geom_on(c)) CDFEM_B3(3, c->d_geom);
         else CDFEM_B3(0, c->d_qd);
 #undef CDFEM_B3
         const hipError_t e = hipGetLastError();
@@ -559,7 +558,6 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv,
     constexpr int S = kBrick * P + 1;
     constexpr int S2 = S * S, S3 = S * S * S;
     constexpr int NC = QLayout<K, 3>::nc;
-    constexpr int NQ = Q1 * Q1 * Q1;
     // LDS patch layout (CDFEM_BRICK_LDS 2, p = 2): rows padded to SY = 12 and planes to SZ = 112 doubles,
     // so the 32 element origins of a ds_read_b64 half-wave (2 ex + 2 SY ey + 2 SZ ez) fall on 16
     // distinct bank pairs (2-way, the floor for even origins) instead of up to 4-way at SY = 9, SZ = 81
@@ -610,7 +608,7 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv,
     const int bx = b % g.nbx, by = (b / g.nbx) % g.nby;
     const int gx0 = (S - 1) * bx, gy0 = (S - 1) * by, gz0 = (S - 1) * bz;
     const bool lastx = bx == g.nbx - 1, lasty = by == g.nby - 1, lastz = bz == g.nbz - 1;
-    const double *q0 = qd + (size_t)b * (AF ? 1 : NQ) * NC * kLanes;  // AF: per-element factors
+    const double *q0 = qd_block<Q1, K, AF>(qd, b);  // AF: per-element factors (3: geometry, pa_geom)
     double den = 0.0;
     // patch gather: every load of the patch is issued before any is consumed (clamped indices,
     // no branches between them): one memory latency per brick instead of one per patch row.
@@ -840,7 +838,7 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv,
             __syncthreads();
         }
     } else {
-        elem_apply3d_af<D1, Q1, K, AF>(xl, q0, t, T, Y);
+        elem_apply3d_af<D1, Q1, K, AF>(xl, q0, t, T, Y, qd);
     }
 
     // element-wise den contribution d0_e . (A_e d0_e) (UM: taken above) and deterministic in-LDS E->L
@@ -1301,7 +1299,8 @@ static hipError_t brick_cg2_launch(cdfem_ctx *c, const double *r, const double *
     g.bzs = run.bzs;
     const dim3 grid((unsigned)(c->nbx * c->nby * run.nlay)), block(64);
     const bool whole = run.nlay == c->nbz && run.s == c->stream;
-    const double *qd = c->d_qaff ? c->d_qaff : c->d_qd;  // (pa_uniform: the element matrix, below)
+    // (pa_uniform: the element matrix, below; pa_geom: the geometry array)
+    const double *qd = c->d_qaff ? c->d_qaff : pa_geom_on(c) ? c->d_geom : c->d_qd;
     const double *upart = c->d_part + c->nblk;  // the den-fold update's partials
     double *const dpart = c->den_out ? c->den_out : c->d_part;  // the apply's den partials
     const int grp = c->den_grp, nbrick = c->nblk;               // (grouped: sums into d_gsum)
@@ -1344,6 +1343,8 @@ static hipError_t brick_cg2_launch(cdfem_ctx *c, const double *r, const double *
         else { CDFEM_BCG4(2, 2, false, false); }
     } else if (pa_af(c) == 1) {
         CDFEM_BCG(1, 1);
+    } else if (pa_geom_on(c)) {
+        CDFEM_BCG(3, 1);
     } else {
         CDFEM_BCG(0, 1);
     }

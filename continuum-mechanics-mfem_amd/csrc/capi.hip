@@ -127,7 +127,7 @@ static bool mesh_is_affine(int dim, int64_t ne, const double *V)
 void free_mesh(cdfem_ctx *c)
 {
     dfree(c->d_verts); dfree(c->d_map); dfree(c->d_e2l_off); dfree(c->d_e2l_pos);
-    dfree(c->d_ess); dfree(c->d_ess_list); dfree(c->d_qd); dfree(c->d_qaff); dfree(c->d_Ye); dfree(c->d_dinv);
+    dfree(c->d_ess); dfree(c->d_ess_list); dfree(c->d_qd); dfree(c->d_qaff); dfree(c->d_geom); dfree(c->d_Ye); dfree(c->d_dinv);
     for (auto &w : c->d_w) dfree(w);
     dfree(c->d_part); dfree(c->d_tpart); dfree(c->d_gm); dfree(c->d_gm_part); dfree(c->d_ktab);
     c->ktab_key = -1;  // rebuilt (and reallocated) by the next k_apply3d_ktile launch
@@ -1417,6 +1417,21 @@ static int pa_setup_form(cdfem_ctx *c, const cdfem_form_coeffs *f)
         dfree(c->d_qaff);
         if (c->pa_affine && c->mesh_affine && !f->kappa_q && !f->kappa_mat_q && !f->conv_q && !f->mass_q)
             c->d_qaff = dalloc<double>((size_t)c->nblk * c->ncomp * kLanes);
+        // pa_geom: a hex mesh the affine forms did not take, constant coefficients, the thread-per-element
+        // applies on the operator rule: the element geometry next to the stream (which the diagonal, the
+        // linear system and a later pa_geom 0 still read).  Any other case keeps the stream alone.
+        dfree(c->d_geom);
+        if (c->pa_geom && c->d_qaff == nullptr && c->dim == 3 && c->qlay == 0 && (c->p == 1 || c->p == 2) &&
+            c->rule_op.q1 == c->p + 2 && !f->kappa_q && !f->kappa_mat_q && !f->conv_q && !f->mass_q) {
+            c->d_geom = dalloc<double>(GeomLayout::kHdr + (size_t)c->nblk * GeomLayout::kNC * kLanes);
+            double hdr[GeomLayout::kHdr] = {};
+            hdr[GeomLayout::hKappa] = f->kappa;
+            for (int i = 0; i < 3; ++i) hdr[GeomLayout::hConv + i] = ((kinds & CDFEM_CONVECTION) && f->conv) ? f->alpha * f->conv[i] : 0.0;
+            hdr[GeomLayout::hMass] = f->mass;
+            for (int q = 0; q < c->rule_op.q1; ++q) hdr[GeomLayout::hPts + q] = c->rule_op.pts[q];
+            HIPCHK(hipMemcpy(c->d_geom, hdr, sizeof(hdr), hipMemcpyHostToDevice));
+            HIPCHK(launch_setup_geom(c));
+        }
         double *dk = upload_opt(c, f->kappa_q, neq), *dkm = upload_opt(c, f->kappa_mat_q, neq * c->dim * (c->dim + 1) / 2);
         double *dc = upload_opt(c, f->conv_q, neq * c->dim), *dm = upload_opt(c, f->mass_q, neq);
         HIPCHK(launch_setup_qdata(c, dk, dkm, f->kappa, f->alpha, f->conv, dc, dm, f->mass));
@@ -1947,6 +1962,11 @@ int cdfem_set_option(cdfem_ctx *c, const char *key, int value)
         } else if (k == "pa_affine") {  // read by cdfem_pa_setup
             if (value < 0 || value > 2) throw ArgError("pa_affine must be 0, 1 or 2");
             c->pa_affine = value;
+        } else if (k == "pa_geom") {  // read by cdfem_pa_setup; 0 afterwards switches back to the stream
+            // (3D hex p <= 2 applies k_apply3d, k_brick3d, k_brick_cg; the p = 3, 4 tile kernels and the 2D
+            // applies keep the stream)
+            if (value != 0 && value != 1) throw ArgError("pa_geom must be 0 or 1");
+            c->pa_geom = value;
         } else if (k == "spmv_lpr") {  // read when the FA pattern is built (once per mesh)
             if (value != 0 && value != 1 && value != 2 && value != 4) throw ArgError("spmv_lpr must be 0 (auto), 1, 2 or 4");
             c->spmv_lpr = value;
@@ -2083,9 +2103,25 @@ int cdfem_kernel_flops(cdfem_ctx *c, int k, double *flops)
         if (kM) { if (kC) pt_fma += 1; else pt_mul += 1; }
         if (c->qlay == 1 ? tile_affine(c) : c->d_qaff != nullptr)
             pt_mul += c->ncomp + 2;  // point data W_q * g_k, W_q = (w_x w_y) w_z
+        double geo_fma = 0.0;  // pa_geom: the hoisted parts of J, 9 FMAs per (z, y) and 9 per z plane
+        if (c->qlay == 0 && pa_geom_on(c)) {
+            // the point operator of elem_apply3d<..., GEO> instead of the one above: two columns of J
+            // (6 FMA), adj(J) (a mul and an FMA per entry; its first row alone without diffusion and
+            // convection), det J (1 mul, 2 FMA), W_q (2 mul); t = adj(J)^T grad u (3 mul, 6 FMA);
+            // D: W kappa / det J (2 mul, the reciprocal counted as 1 division), the scaled t (3 mul),
+            // adj(J) t (3 mul, 6 FMA); C: W (alpha c . t) (2 mul, 2 FMA); M: W s det J (2 mul) and its
+            // product with u (an FMA after C, else a mul)
+            const int na = g ? 9 : 3;
+            pt_fma = D * (1 + 3 * g) + D * (kD ? 4 : 1);
+            pt_mul = 0.0;
+            pt_fma += 6 + na + 2 + (g ? 6 : 0) + (kD ? 6 : 0) + (kC ? 2 : 0) + ((kM && kC) ? 1 : 0);
+            pt_mul += na + 1 + 2 + (g ? 3 : 0) + (kD ? 2 + 1 + 3 + 3 : 0) + (kC ? 2 : 0) + (kM ? 2 : 0) +
+                      ((kM && !kC) ? 1 : 0);
+            geo_fma = (double)Q * (9 + 9 * Q);
+        }
         const double fma = Q * ((double)D * D * D * (1 + g) + Q * ((double)D * D * (1 + 2 * g) + Q * pt_fma +
                                                                    (double)D * D * (kD ? 3 : 1)) +
-                                (double)D * D * D * (kD ? 2 : 1));
+                                (double)D * D * D * (kD ? 2 : 1)) + geo_fma;
         const double mul = (double)Q * Q * Q * pt_mul;
         *flops = (2.0 * fma + mul) * (double)c->ne;
         return CDFEM_OK;
@@ -2145,7 +2181,10 @@ int cdfem_kernel_bytes(cdfem_ctx *c, int k, double *bytes)
                                   // flags + d (each dof by its one writer brick) + patch outputs
                                   // (+ x read and written by its writer brick under the x-fold)
                 // (pa_uniform: one element matrix, 14 x 64 operand doubles, instead of the factor stream)
-                *bytes = (uniform_elem(c) ? 8.0 * 14 * 64 : 8.0 * c->ncomp * (c->d_qaff ? 1.0 : nq) * ne) + 24.0 * nl +
+                // (pa_geom: the element's mask and 21 map coefficients instead of its stream)
+                *bytes = (uniform_elem(c) ? 8.0 * 14 * 64
+                          : pa_geom_on(c) ? 8.0 * GeomLayout::kNC * ne
+                                          : 8.0 * c->ncomp * (c->d_qaff ? 1.0 : nq) * ne) + 24.0 * nl +
                          1.0 * nl + 8.0 * nl + patches + (xf ? 16.0 * nl : 0.0);
                 return CDFEM_OK;
             case CDFEM_K_E2L:     // the Mult's row sums: the patch buffer + ess flags + y (brick_mult_pb,
@@ -2169,7 +2208,10 @@ int cdfem_kernel_bytes(cdfem_ctx *c, int k, double *bytes)
                          (tile_dfold_ok(c) ? 16.0 * nl : 0.0);  // CG apply with the direction fold:
                                                                 // + d_old gather, + d store
             else             // x gather (each L-dof once) + qdata stream + element map + E-vector write
-                *bytes = 8.0 * nl + 8.0 * c->ncomp * nqs * ne + 4.0 * nd * ne + 8.0 * nd * ne;
+                             // (pa_geom: the element's mask and 21 map coefficients instead of its stream)
+                *bytes = 8.0 * nl + (c->qlay == 0 && c->dim == 3 && pa_geom_on(c) ? 8.0 * GeomLayout::kNC * ne
+                                                                                  : 8.0 * c->ncomp * nqs * ne) +
+                         4.0 * nd * ne + 8.0 * nd * ne;
             break;
         case CDFEM_K_E2L:
             if (c->epencil)  // E-vector read + ess flags + y write + x read (constraint / dot)

@@ -306,6 +306,11 @@ struct cdfem_ctx {
     int pa_affine = 2;                  // set_option "pa_affine": when the mesh allows, 1 form the point data
                                         // from the affine factors, 2 the Kronecker form of the same factors
                                         // (3D p <= 2 applies; the p >= 3 tile apply takes 2 as 1); 0 stream
+    int pa_geom = 0;                    // set_option "pa_geom": 1 = on a hex mesh the affine forms do not take (3D
+                                        // p <= 2, constant coefficients) the applies form the point data from the
+                                        // element's trilinear map (AF 3) instead of streaming it; read by
+                                        // cdfem_pa_setup, 0 afterwards switches back to the stream
+    double *d_geom = nullptr;           // pa_geom: header + [nblk][22][64] masks and map coefficients (GeomLayout)
     double *d_Ye = nullptr;             // [nblk][nd][64]
     double *d_dinv = nullptr;           // Jacobi (constrained: ess -> 1)
     bool dinv_ready = false;
@@ -363,6 +368,12 @@ inline bool tile_kron(const cdfem_ctx *c) { return c->d_qaff != nullptr && c->ho
 // the element core of the 3D p <= 2 applies (pa_core.hpp elem_apply3d_af): 0 per-point stream,
 // 1 point data from the affine factors, 2 Kronecker form of the factors
 inline int pa_af(const cdfem_ctx *c) { return c->d_qaff == nullptr ? 0 : (c->pa_affine == 2 ? 2 : 1); }
+// pa_geom taken by the setup and still on: the 3D p <= 2 applies run the AF 3 core on d_geom
+inline bool pa_geom_on(const cdfem_ctx *c) { return c->d_geom != nullptr && c->pa_geom != 0 && c->d_qaff == nullptr; }
+// the form the 3D p <= 2 apply kernels are launched with (their AF argument): pa_af, or 3 under pa_geom.
+// Everything else that asks for the form (folds, patch buffers, accounting of the other kernels) asks
+// pa_af: AF 3 runs wherever the stream (AF 0) does, with the same launch structure.
+inline int pa_form(const cdfem_ctx *c) { return pa_geom_on(c) ? 3 : pa_af(c); }
 // the brick CG applies the common element matrix of a uniform box (pa_uniform: formed at the PA setup;
 // set_option "pa_uniform" 0 switches back to the Kronecker form without a new setup)
 inline bool uniform_elem(const cdfem_ctx *c) { return c->d_uelem != nullptr && c->pa_uniform != 0 && pa_af(c) == 2; }
@@ -371,6 +382,8 @@ inline bool uniform_elem(const cdfem_ctx *c) { return c->d_uelem != nullptr && c
 hipError_t launch_setup_qdata(cdfem_ctx *c, const double *d_kappa_q, const double *d_kmat_q, double kappa, double alpha,
                               const double *conv, const double *d_conv_q, const double *d_mass_q,
                               double mass);
+// pa_geom: fills d_geom's blocks from the vertices (the header is the caller's)
+hipError_t launch_setup_geom(cdfem_ctx *c);
 hipError_t launch_apply(cdfem_ctx *c, const double *x, double *Ye, bool constrained);
 hipError_t launch_apply_wpe(cdfem_ctx *c, const double *x, double *Ye, bool con, const KrylovState *st);
 hipError_t launch_apply_st(cdfem_ctx *c, const double *x, double *Ye, bool constrained,

@@ -147,6 +147,48 @@ __device__ __forceinline__ void load_qp(const double *__restrict__ qp, int lane,
     }
 }
 
+// pa_geom (cdfem_ctx::d_geom): the geometry the element core needs to form a hex's point data itself.
+// A header of kHdr doubles (the constants of the form and the rule's 1D points, read through uniform
+// addresses) and then per block [kNC][kLanes]: the lane's mask (1, padding lanes 0) and the
+// coefficients a1..a7 of its trilinear map (the translation a0 does not enter the Jacobian and is not
+// kept).  8 * 22 = 176 B per element against the stream's 8 NQ NC.
+struct GeomLayout {
+    static constexpr int kHdr = 16;   // 128 B: the blocks start on a cache line
+    static constexpr int hKappa = 0, hConv = 1, hMass = 4, hPts = 8;  // kappa, alpha c (3), s; points (<= 8)
+    static constexpr int kNC = 22;
+    static constexpr int oLive = 0, oA = 1;  // a_m component i at oA + 3 (m - 1) + i
+};
+
+// doubles per element block of what an apply reads through qd, by form (AF 0 stream, 1 / 2 affine
+// factors, 3 geometry), and the block's first double
+template <int Q1, unsigned K, int AF>
+__host__ __device__ constexpr size_t qd_block_doubles()
+{
+    return (size_t)(AF == 3 ? GeomLayout::kNC : (AF ? 1 : Q1 * Q1 * Q1) * QLayout<K, 3>::nc) * kLanes;
+}
+template <int Q1, unsigned K, int AF>
+__device__ __forceinline__ const double *qd_block(const double *__restrict__ qd, int b)
+{
+    return qd + (AF == 3 ? GeomLayout::kHdr : 0) + (size_t)b * qd_block_doubles<Q1, K, AF>();
+}
+
+// 1 / x to rounding error: the hardware estimate and two Newton steps (6 instructions against the 11
+// of the IEEE division; x = det J of a valid element, far from the ends of the exponent range)
+__device__ __forceinline__ double rcp_nr(double x)
+{
+    double r = __builtin_amdgcn_rcp(x);
+    r = __builtin_fma(r, __builtin_fma(-x, r, 1.0), r);
+    r = __builtin_fma(r, __builtin_fma(-x, r, 1.0), r);
+    return r;
+}
+
+__device__ __forceinline__ void cross3(const double (&u)[3], const double (&v)[3], double (&w)[3])
+{
+    w[0] = u[1] * v[2] - u[2] * v[1];
+    w[1] = u[2] * v[0] - u[0] * v[2];
+    w[2] = u[0] * v[1] - u[1] * v[0];
+}
+
 // Y = A_e X for one element: X, Y lexicographic [dz][dy][dx]; q0 points at this element's
 // block's qdata (q = 0, lane 0; point stride NC * kLanes), lane = element.  X is read through the
 // loader xl(dz, dy, dx) once per quadrature plane, so a caller holding X in LDS keeps only one
@@ -156,16 +198,43 @@ __device__ __forceinline__ void load_qp(const double *__restrict__ qp, int lane,
 // AFF (affine elements, constant coefficients): q0 points at the block's per-element factors
 // [NC][kLanes] instead, and the point data is formed as W_q * G_k, the same product the setup
 // stores (k_setup_qdata, aff), so both forms apply the same operator bit for bit.
-template <int D1, int Q1, unsigned K, typename XL, int QZU = Q1, bool AFF = false>
+// GEO (pa_geom: any hex, constant coefficients): q0 points at the block's per-element geometry
+// [GeomLayout::kNC][kLanes] and gc at the array's header; the point operator is formed in registers
+// from the trilinear map, D = W kappa adj(J) adj(J)^T / det J, C = W alpha adj(J) c, M = W s det J, the
+// values k_setup_qdata stores (to rounding: J comes from the map's coefficients, not the vertex sum,
+// and D, C are applied in their factors adj(J), adj(J)^T without being multiplied out).
+// With x = a0 + a1 xi + a2 eta + a3 zeta + a4 xi eta + a5 xi zeta + a6 eta zeta + a7 xi eta zeta:
+//     dx/dxi   = (a1 + a5 zeta) + eta (a4 + a7 zeta)          per (qz, qy)
+//     dx/deta  = (a2 + a6 zeta) + xi (a4 + a7 zeta)           3 FMAs per point
+//     dx/dzeta = (a3 + a6 eta) + xi (a5 + a7 eta)             3 FMAs per point
+// The rows of adj(J) are the cross products of these columns.  A padding lane holds the unit cube and
+// the mask 0, which enters the three constants: its point data are exact zeros, with det J = 1.
+template <int D1, int Q1, unsigned K, typename XL, int QZU = Q1, bool AFF = false, bool GEO = false>
 __device__ __forceinline__ void elem_apply3d(const XL &xl, const double *__restrict__ q0, int lane,
-                                             const Tab<D1, Q1> &T, double (&Y)[D1][D1][D1])
+                                             const Tab<D1, Q1> &T, double (&Y)[D1][D1][D1],
+                                             const double *__restrict__ gc = nullptr)
 {
     using L = QLayout<K, 3>;
     constexpr int NC = L::nc;
-    double ga[NC];
+    static_assert(!(AFF && GEO), "one form of the point data");
+    double ga[AFF ? NC : 1];
     if constexpr (AFF) {
 #pragma unroll
         for (int k = 0; k < NC; ++k) ga[k] = q0[k * kLanes + lane];
+    }
+    // GEO: the map's coefficients a1..a7 (ma[m - 1][i]) and the masked constants
+    double ma[GEO ? 7 : 1][3];
+    double gkap = 0.0, gac[3] = {0.0, 0.0, 0.0}, gs = 0.0;
+    if constexpr (GEO) {
+        const double live = q0[GeomLayout::oLive * kLanes + lane];
+#pragma unroll
+        for (int m = 0; m < 7; ++m)
+#pragma unroll
+            for (int i = 0; i < 3; ++i) ma[m][i] = q0[(GeomLayout::oA + 3 * m + i) * kLanes + lane];
+        gkap = gc[GeomLayout::hKappa] * live;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) gac[i] = gc[GeomLayout::hConv + i] * live;
+        gs = gc[GeomLayout::hMass] * live;
     }
 #pragma unroll
     for (int dz = 0; dz < D1; ++dz)
@@ -176,6 +245,16 @@ __device__ __forceinline__ void elem_apply3d(const XL &xl, const double *__restr
 
 #pragma unroll QZU
     for (int qz = 0; qz < Q1; ++qz) {
+        double e1[3], e2[3], e4[3];  // GEO: a1 + a5 zeta, a2 + a6 zeta, a4 + a7 zeta
+        if constexpr (GEO) {
+            const double zeta = gc[GeomLayout::hPts + qz];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                e1[i] = ma[0][i] + zeta * ma[4][i];
+                e2[i] = ma[1][i] + zeta * ma[5][i];
+                e4[i] = ma[3][i] + zeta * ma[6][i];
+            }
+        }
         // contract z
         double T0[D1][D1], Tz[D1][D1];
 #pragma unroll
@@ -200,6 +279,16 @@ __device__ __forceinline__ void elem_apply3d(const XL &xl, const double *__restr
 
 #pragma unroll
         for (int qy = 0; qy < Q1; ++qy) {
+            double c0[3], f3[3], f5[3];  // GEO: dx/dxi, a3 + a6 eta, a5 + a7 eta
+            if constexpr (GEO) {
+                const double eta = gc[GeomLayout::hPts + qy];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    c0[i] = e1[i] + eta * e4[i];
+                    f3[i] = ma[2][i] + eta * ma[5][i];
+                    f5[i] = ma[4][i] + eta * ma[6][i];
+                }
+            }
             // contract y
             double a[D1], ay[D1], az[D1];
 #pragma unroll
@@ -228,23 +317,56 @@ __device__ __forceinline__ void elem_apply3d(const XL &xl, const double *__restr
                     uy += T.B[qx][dx] * ay[dx];
                     uz += T.B[qx][dx] * az[dx];
                 }
-                double qv[NC];
-                if constexpr (AFF) {
-                    const double W = T.w[qx] * T.w[qy] * T.w[qz];
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) qv[k] = W * ga[k];
-                } else {
-                    const int q = qx + Q1 * (qy + Q1 * qz);
-                    load_qp<NC, true>(q0 + (size_t)q * NC * kLanes, lane, qv);
-                }
                 double vv = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
-                if constexpr (L::kD) {
-                    gx = qv[0] * ux + qv[1] * uy + qv[2] * uz;
-                    gy = qv[1] * ux + qv[3] * uy + qv[4] * uz;
-                    gz = qv[2] * ux + qv[4] * uy + qv[5] * uz;
+                if constexpr (GEO) {
+                    const double xi = gc[GeomLayout::hPts + qx];
+                    const double W = T.w[qx] * T.w[qy] * T.w[qz];
+                    double c1[3], c2[3];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        c1[i] = e2[i] + xi * e4[i];
+                        c2[i] = f3[i] + xi * f5[i];
+                    }
+                    double A[3][3];  // adj(J): rows c1 x c2, c2 x c0, c0 x c1
+                    cross3(c1, c2, A[0]);
+                    const double det = c0[0] * A[0][0] + c0[1] * A[0][1] + c0[2] * A[0][2];
+                    // the point operator without its matrix: t = adj(J)^T grad_ref u (det J times the
+                    // physical gradient), then D grad_ref u = (W kappa / det J) adj(J) t and
+                    // C . grad_ref u = W (alpha c) . t: 21 + 4 operations against 33 + 15 through D and C
+                    double t[3] = {0.0, 0.0, 0.0};
+                    if constexpr (L::kD || L::kC) {
+                        cross3(c2, c0, A[1]);
+                        cross3(c0, c1, A[2]);
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) t[k] = A[0][k] * ux + A[1][k] * uy + A[2][k] * uz;
+                    }
+                    if constexpr (L::kD) {
+                        const double sd = W * gkap * rcp_nr(det);
+                        const double w0 = sd * t[0], w1 = sd * t[1], w2 = sd * t[2];
+                        gx = A[0][0] * w0 + A[0][1] * w1 + A[0][2] * w2;
+                        gy = A[1][0] * w0 + A[1][1] * w1 + A[1][2] * w2;
+                        gz = A[2][0] * w0 + A[2][1] * w1 + A[2][2] * w2;
+                    }
+                    if constexpr (L::kC) vv = W * (gac[0] * t[0] + gac[1] * t[1] + gac[2] * t[2]);
+                    if constexpr (L::kM) vv += (W * gs * det) * u;
+                } else {
+                    double qv[NC];
+                    if constexpr (AFF) {
+                        const double W = T.w[qx] * T.w[qy] * T.w[qz];
+#pragma unroll
+                        for (int k = 0; k < NC; ++k) qv[k] = W * ga[k];
+                    } else {
+                        const int q = qx + Q1 * (qy + Q1 * qz);
+                        load_qp<NC, true>(q0 + (size_t)q * NC * kLanes, lane, qv);
+                    }
+                    if constexpr (L::kD) {
+                        gx = qv[0] * ux + qv[1] * uy + qv[2] * uz;
+                        gy = qv[1] * ux + qv[3] * uy + qv[4] * uz;
+                        gz = qv[2] * ux + qv[4] * uy + qv[5] * uz;
+                    }
+                    if constexpr (L::kC) vv = qv[L::oC] * ux + qv[L::oC + 1] * uy + qv[L::oC + 2] * uz;
+                    if constexpr (L::kM) vv += qv[L::oM] * u;
                 }
-                if constexpr (L::kC) vv = qv[L::oC] * ux + qv[L::oC + 1] * uy + qv[L::oC + 2] * uz;
-                if constexpr (L::kM) vv += qv[L::oM] * u;
                 // transposed contraction in x
 #pragma unroll
                 for (int dx = 0; dx < D1; ++dx) {
@@ -490,12 +612,17 @@ __device__ __forceinline__ void elem_apply3d_kron(const XL &xl, const double *__
 }
 
 // the element core of the apply kernels by affine form: AF 0 per-point stream, 1 point data formed
-// from the affine factors (elem_apply3d<..., AFF>), 2 the Kronecker form of the same factors
+// from the affine factors (elem_apply3d<..., AFF>), 2 the Kronecker form of the same factors, 3 point
+// data formed from the hex's trilinear map (pa_geom; gc = the geometry array's header)
 template <int D1, int Q1, unsigned K, int AF, typename XL>
 __device__ __forceinline__ void elem_apply3d_af(const XL &xl, const double *__restrict__ q0, int lane,
-                                                const Tab<D1, Q1> &T, double (&Y)[D1][D1][D1])
+                                                const Tab<D1, Q1> &T, double (&Y)[D1][D1][D1],
+                                                const double *__restrict__ gc = nullptr)
 {
     if constexpr (AF == 2) elem_apply3d_kron<D1, Q1, K>(xl, q0, lane, T, Y);
+    // (p = 2: the quadrature planes as a loop, or the scheduler lifts every plane's geometry to the top
+    // and the kernel spills past 512 registers)
+    else if constexpr (AF == 3) elem_apply3d<D1, Q1, K, XL, (D1 >= 3 ? 1 : Q1), false, true>(xl, q0, lane, T, Y, gc);
     else elem_apply3d<D1, Q1, K, XL, Q1, AF == 1>(xl, q0, lane, T, Y);
 }
 

@@ -29,10 +29,7 @@ k_apply3d(const int32_t *__restrict__ map, const double *__restrict__ x,
           const int nblk, const KrylovState *__restrict__ st)
 {
     if (st != nullptr && st->done) return;
-    using L = QLayout<K, 3>;
     constexpr int ND = D1 * D1 * D1;
-    constexpr int NQ = Q1 * Q1 * Q1;
-    constexpr int NC = L::nc;
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (b >= nblk) return;
@@ -56,10 +53,11 @@ k_apply3d(const int32_t *__restrict__ map, const double *__restrict__ x,
             }
 
     double Y[D1][D1][D1];
-    // AF: qd holds the block's affine factors [NC][kLanes] (pa_affine), else the per-point stream
-    const double *q0 = qd + (size_t)b * (AF ? 1 : NQ) * NC * kLanes;
+    // AF: qd holds the block's affine factors [NC][kLanes] (pa_affine) or, AF 3, the geometry array
+    // (pa_geom: header + [GeomLayout::kNC][kLanes] per block), else the per-point stream
+    const double *q0 = qd_block<Q1, K, AF>(qd, b);
     auto xl = [&](int dz, int dy, int dx) { return X[dz][dy][dx]; };
-    elem_apply3d_af<D1, Q1, K, AF>(xl, q0, lane, T, Y);
+    elem_apply3d_af<D1, Q1, K, AF>(xl, q0, lane, T, Y, qd);
 
     double *yp = Ye + (size_t)b * ND * kLanes + lane;
 #pragma unroll
@@ -352,6 +350,37 @@ k_setup_qdata(const double *__restrict__ verts, const int32_t *__restrict__ perm
     if (kinds & CDFEM_MASS) {
         const double s = mass_q ? mass_q[eq] : mass;
         put(o++, W * s * det);
+    }
+}
+
+// pa_geom: the per-element geometry of the AF 3 element core (pa_core.hpp GeomLayout), thread per
+// (block, lane): the mask and the coefficients a1..a7 of the hex's trilinear map (lexicographic
+// vertices: bit k of the vertex number = its position along axis k).  Padding lanes: the unit cube, mask 0.
+__global__ void __launch_bounds__(256)
+k_setup_geom(const double *__restrict__ verts, const int32_t *__restrict__ perm, int ne, int nblk,
+             double *__restrict__ geom)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)nblk * kLanes) return;
+    const int lane = (int)(t % kLanes), b = (int)(t / kLanes);
+    const int e = perm[t];
+    double *out = geom + GeomLayout::kHdr + (size_t)b * GeomLayout::kNC * kLanes + lane;
+    const bool live = e >= 0 && e < ne;
+    out[GeomLayout::oLive * kLanes] = live ? 1.0 : 0.0;
+    const double *V = verts + (size_t)(live ? e : 0) * 24;
+    for (int i = 0; i < 3; ++i) {
+        const double v0 = V[i], v1 = V[3 + i], v2 = V[6 + i], v3 = V[9 + i];
+        const double v4 = V[12 + i], v5 = V[15 + i], v6 = V[18 + i], v7 = V[21 + i];
+        double a[7];
+        a[0] = v1 - v0;
+        a[1] = v2 - v0;
+        a[2] = v4 - v0;
+        a[3] = (v3 - v2) - (v1 - v0);
+        a[4] = (v5 - v4) - (v1 - v0);
+        a[5] = (v6 - v4) - (v2 - v0);
+        a[6] = ((v7 - v6) - (v5 - v4)) - ((v3 - v2) - (v1 - v0));
+        for (int m = 0; m < 7; ++m)
+            out[(GeomLayout::oA + 3 * m + i) * kLanes] = live ? a[m] : (m == i ? 1.0 : 0.0);
     }
 }
 
@@ -736,6 +765,14 @@ hipError_t launch_setup_qdata(cdfem_ctx *c, const double *d_kappa_q, const doubl
     return hipGetLastError();
 }
 
+hipError_t launch_setup_geom(cdfem_ctx *c)
+{
+    const int64_t n = (int64_t)c->nblk * kLanes;
+    hipLaunchKernelGGL(k_setup_geom, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, c->d_verts, c->d_perm, c->ne,
+                       c->nblk, c->d_geom);
+    return hipGetLastError();
+}
+
 hipError_t launch_quad_points(cdfem_ctx *c, const Rule1D &r, double *xyz)
 {
     const int nq = c->dim == 3 ? r.q1 * r.q1 * r.q1 : r.q1 * r.q1;
@@ -841,15 +878,17 @@ static hipError_t apply_kinds(cdfem_ctx *c, const double *x, double *Ye, bool co
     const Tab<D1, Q1> T = make_tab<D1, Q1>(c->rule_op);
     const dim3 grid(grid_for(c->nblk, 4)), block(256);
     if constexpr (DIM == 3) {
-        const int af = pa_af(c);
-        const double *qd = af ? c->d_qaff : c->d_qd;
+        const int af = pa_form(c);
+        const double *qd = af == 3 ? c->d_geom : af ? c->d_qaff : c->d_qd;
 #define CDFEM_A3(CON_, AF_)                                                                                  \
     hipLaunchKernelGGL((k_apply3d<D1, Q1, K, CON_, AF_>), grid, block, 0, c->stream, c->d_map, x, qd, Ye, T, \
                        c->nblk, st)
         if (con) {
-            if (af == 2) CDFEM_A3(true, 2); else if (af == 1) CDFEM_A3(true, 1); else CDFEM_A3(true, 0);
+            if (af == 3) CDFEM_A3(true, 3); else if (af == 2) CDFEM_A3(true, 2); else if (af == 1) CDFEM_A3(true, 1);
+            else CDFEM_A3(true, 0);
         } else {
-            if (af == 2) CDFEM_A3(false, 2); else if (af == 1) CDFEM_A3(false, 1); else CDFEM_A3(false, 0);
+            if (af == 3) CDFEM_A3(false, 3); else if (af == 2) CDFEM_A3(false, 2); else if (af == 1) CDFEM_A3(false, 1);
+            else CDFEM_A3(false, 0);
         }
 #undef CDFEM_A3
     } else {

@@ -347,6 +347,31 @@ int cdfem_fp64_bench(cdfem_ctx *ctx, int mode, int reps, double *tflops);
  *                data.  All forms apply the operator of the per-point multilinear-map setup to rounding
  *                (the Kronecker form is an algebraic identity of the tensor rule, not an exactness
  *                argument); 0 = the per-point map and stream everywhere.
+ * "pa_geom": 0 (default) or 1 — read by cdfem_pa_setup: geometric factors formed inside the apply on hex
+ *              meshes the affine forms do not take (a perturbed box, a moved mesh).  With 1 the setup keeps,
+ *              next to the per-point stream, 22 doubles per element (a padding mask and the coefficients
+ *              a1..a7 of the element's trilinear map, 176 B against the stream's 5,120 B at p = 2, kinds 7),
+ *              and the 3D p <= 2 applies — the generic element-block apply k_apply3d, the structured Mult
+ *              k_brick3d (GMRES, cdfem_pa_mult) and the structured CG apply k_brick_cg, on one rank or on
+ *              slabs — form J, adj(J), det J and D = W kappa adj(J) adj(J)^T / det J, C = W alpha adj(J) c,
+ *              M = W s det J in registers at every point (pa_core.hpp elem_apply3d<..., GEO>; the operator of
+ *              the stream to rounding, one division per point).  Taken when all of these hold: hex mesh,
+ *              dim 3, p = 1 or 2 with the operators' rule (q1 = p + 2); every coefficient constant (kappa_q,
+ *              kappa_mat_q, conv_q and mass_q all NULL); the affine form not taken (mesh not affine, or
+ *              "pa_affine" 0).  On an affine mesh with pa_affine != 0 the Kronecker form stays, and in every
+ *              other case (per-point coefficients, p = 3, 4: the high-order tile kernels, 2D) the setup keeps
+ *              the stream without a word.  The stream is still allocated and filled (the diagonal,
+ *              FormLinearSystem and the 2D paths read it), so 0 after a setup switches back without a new
+ *              setup; 1 needs one.  The kernels run with the stream's launch structure (one wave per SIMD, no
+ *              CG folds), 476 registers at p = 2 kinds 7 without scratch.  The MFEM-shaped C++ layer
+ *              (cpp/cdfem_mfem.hpp) has no option channel and keeps the default.
+ *              Measured on the perturbed C2 box (64^3, p = 2, perturb 0.1; tools/ab_geom.py, DESIGN.md 4.1,
+ *              profiles/r08/ab_c2_geom_fly/), pa_geom 1 against 0 on the same box in one process, kinds 7:
+ *              CG apply 95.4 against 240.6 us, CG 1.39e10 against 7.14e9 DoF-iter/s, GMRES(30) 9.05e9 against
+ *              5.98e9; apply bytes 140.9 MB against 1,436.9 MB, flops 3.12 G against 1.85 G (32.7 TFLOP/s,
+ *              0.42 of the f64 peak: the apply is VALU-bound).  Kinds 5: apply 92.9 against 178.1 us, CG
+ *              1.43e10 against 9.04e9.  Iterates agree to 3e-15.  Not measured: the generic element-block
+ *              apply, p = 1, several ranks (parity-tested only), and no counter pass was taken.
  * "cg_xfold": 1 (default) — structured brick CG (p <= 2, Kronecker form): each apply after the first
  *             advances x by the previous iteration's alpha d on the dofs it writes the new direction
  *             for, so the update kernel streams neither x nor d (bitwise the same iterates; 1 % faster
@@ -406,11 +431,13 @@ int cdfem_profile_read(cdfem_ctx *ctx, int kernel, double *total_ms, int64_t *co
 int cdfem_profile_launches(cdfem_ctx *ctx, int kernel, double *ms, int64_t cap, int64_t *count);
 /* algorithmic bytes moved by one launch of kernel id (see DESIGN.md for the per-unit figures); on
  * structured boxes the figure is that of the kernel the CG solve launches (the brick CG kernels, the
- * fused high-order apply with its direction fold)                                                 */
+ * fused high-order apply with its direction fold); under pa_geom the apply's 176 B of geometry per
+ * element replace the per-point stream's 8 nq nc                                                   */
 int cdfem_kernel_bytes(cdfem_ctx *ctx, int kernel, double *bytes);
 /* algorithmic f64 flops of one launch of the 3D partial-assembly apply (CDFEM_K_APPLY; FMA = 2):
- * the sum-factorized element apply (plus the point data W_q * g_e under pa_affine 1), or the
- * Kronecker-form element apply under pa_affine 2                                 */
+ * the sum-factorized element apply (plus the point data W_q * g_e under pa_affine 1, or the point
+ * operator formed from the element's trilinear map under pa_geom, its reciprocal counted as 1), or
+ * the Kronecker-form element apply under pa_affine 2                             */
 int cdfem_kernel_flops(cdfem_ctx *ctx, int kernel, double *flops);
 /* the HIP kernel name (without template arguments) kernel id runs as in the current configuration,
  * as rocprof reports it: the operator apply of a CG solve (CDFEM_K_APPLY) only — the SpMV after
