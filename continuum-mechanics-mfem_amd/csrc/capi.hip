@@ -127,7 +127,7 @@ static bool mesh_is_affine(int dim, int64_t ne, const double *V)
 void free_mesh(cdfem_ctx *c)
 {
     dfree(c->d_verts); dfree(c->d_map); dfree(c->d_e2l_off); dfree(c->d_e2l_pos);
-    dfree(c->d_ess); dfree(c->d_ess_list); dfree(c->d_qd); dfree(c->d_qaff); dfree(c->d_geom); dfree(c->d_Ye); dfree(c->d_dinv);
+    dfree(c->d_ess); dfree(c->d_ess_list); dfree(c->d_qd); dfree(c->d_qaff); dfree(c->d_geom); dfree(c->d_hgeom); dfree(c->d_Ye); dfree(c->d_dinv);
     for (auto &w : c->d_w) dfree(w);
     dfree(c->d_part); dfree(c->d_tpart); dfree(c->d_gm); dfree(c->d_gm_part); dfree(c->d_ktab);
     c->ktab_key = -1;  // rebuilt (and reallocated) by the next k_apply3d_ktile launch
@@ -1432,6 +1432,20 @@ static int pa_setup_form(cdfem_ctx *c, const cdfem_form_coeffs *f)
             HIPCHK(hipMemcpy(c->d_geom, hdr, sizeof(hdr), hipMemcpyHostToDevice));
             HIPCHK(launch_setup_geom(c));
         }
+        // ho_geom: the same for the p = 3, 4 tile apply, element-major (whether the apply takes it also
+        // depends on ho_mfma when it runs: ho_geom_on)
+        dfree(c->d_hgeom);
+        if (c->ho_geom && c->d_qaff == nullptr && c->dim == 3 && c->qlay == 1 && (c->p == 3 || c->p == 4) &&
+            c->rule_op.q1 == c->p + 2 && !f->kappa_q && !f->kappa_mat_q && !f->conv_q && !f->mass_q) {
+            c->d_hgeom = dalloc<double>(GeomLayout::kHdr + (size_t)c->ne * HoGeomLayout::kNC);
+            double hdr[GeomLayout::kHdr] = {};
+            hdr[GeomLayout::hKappa] = f->kappa;
+            for (int i = 0; i < 3; ++i) hdr[GeomLayout::hConv + i] = ((kinds & CDFEM_CONVECTION) && f->conv) ? f->alpha * f->conv[i] : 0.0;
+            hdr[GeomLayout::hMass] = f->mass;
+            for (int q = 0; q < c->rule_op.q1; ++q) hdr[GeomLayout::hPts + q] = c->rule_op.pts[q];
+            HIPCHK(hipMemcpy(c->d_hgeom, hdr, sizeof(hdr), hipMemcpyHostToDevice));
+            HIPCHK(launch_setup_hgeom(c));
+        }
         double *dk = upload_opt(c, f->kappa_q, neq), *dkm = upload_opt(c, f->kappa_mat_q, neq * c->dim * (c->dim + 1) / 2);
         double *dc = upload_opt(c, f->conv_q, neq * c->dim), *dm = upload_opt(c, f->mass_q, neq);
         HIPCHK(launch_setup_qdata(c, dk, dkm, f->kappa, f->alpha, f->conv, dc, dm, f->mass));
@@ -1967,6 +1981,10 @@ int cdfem_set_option(cdfem_ctx *c, const char *key, int value)
             // applies keep the stream)
             if (value != 0 && value != 1) throw ArgError("pa_geom must be 0 or 1");
             c->pa_geom = value;
+        } else if (k == "ho_geom") {  // read by cdfem_pa_setup; 0 afterwards switches back to the stream
+            // (the 3D hex p = 3, 4 tile apply k_apply3d_tile where it runs the stream with ho_mfma 0)
+            if (value != 0 && value != 1) throw ArgError("ho_geom must be 0 or 1");
+            c->ho_geom = value;
         } else if (k == "spmv_lpr") {  // read when the FA pattern is built (once per mesh)
             if (value != 0 && value != 1 && value != 2 && value != 4) throw ArgError("spmv_lpr must be 0 (auto), 1, 2 or 4");
             c->spmv_lpr = value;
@@ -2119,10 +2137,27 @@ int cdfem_kernel_flops(cdfem_ctx *c, int k, double *flops)
                       ((kM && !kC) ? 1 : 0);
             geo_fma = (double)Q * (9 + 9 * Q);
         }
+        double geo_mul = 0.0;
+        if (c->qlay == 1 && ho_geom_on(c)) {
+            // k_apply3d_tile<..., MF 32>: the same point operator with the tile's hoisting.  Per point 32 FMAs
+            // and 27 multiplications on top of the contractions at kinds 7: two columns of J from the column's
+            // hoisted parts (6 FMA), adj(J) (a mul and an FMA per entry; its first row alone without
+            // diffusion and convection), det J (1 mul, 2 FMA), W_q = (w_x w_y) w_z (1 mul); t, D, C, M as
+            // above.  Per column of points (thread), once: a1 + eta a4, a5 + eta a7, a2 + xi a4, a6 + xi a7
+            // (12 FMA), dx/dzeta (6 FMA), w_x w_y (1 mul).
+            const int na = g ? 9 : 3;
+            pt_fma = D * (1 + 3 * g) + D * (kD ? 4 : 1);
+            pt_mul = 0.0;
+            pt_fma += 6 + na + 2 + (g ? 6 : 0) + (kD ? 6 : 0) + (kC ? 2 : 0) + ((kM && kC) ? 1 : 0);
+            pt_mul += na + 1 + 1 + (g ? 3 : 0) + (kD ? 2 + 1 + 3 + 3 : 0) + (kC ? 2 : 0) + (kM ? 2 : 0) +
+                      ((kM && !kC) ? 1 : 0);
+            geo_fma = (double)Q * Q * 18;
+            geo_mul = (double)Q * Q;
+        }
         const double fma = Q * ((double)D * D * D * (1 + g) + Q * ((double)D * D * (1 + 2 * g) + Q * pt_fma +
                                                                    (double)D * D * (kD ? 3 : 1)) +
                                 (double)D * D * D * (kD ? 2 : 1)) + geo_fma;
-        const double mul = (double)Q * Q * Q * pt_mul;
+        const double mul = (double)Q * Q * Q * pt_mul + geo_mul;
         *flops = (2.0 * fma + mul) * (double)c->ne;
         return CDFEM_OK;
     });
@@ -2201,15 +2236,18 @@ int cdfem_kernel_bytes(cdfem_ctx *c, int k, double *bytes)
         }
         // the 3D applies on affine factors read one factor set per element (the 2D apply streams)
         const double nqs = (c->qlay == 1 ? tile_affine(c) : (c->dim == 3 && c->d_qaff != nullptr)) ? 1.0 : nq;
+        // (ho_geom: the tile apply reads the element's 24 doubles of map coefficients instead of its stream)
+        const bool hgeo = c->qlay == 1 && ho_geom_on(c);
         switch (k) {
         case CDFEM_K_APPLY:
             if (c->epencil)  // lattice gather: x + ess flags (each L-dof once) + qdata + E-vector write
-                *bytes = 9.0 * nl + 8.0 * c->ncomp * nqs * ne + 8.0 * nd * ne +
+                *bytes = 9.0 * nl + (hgeo ? 8.0 * HoGeomLayout::kNC * ne : 8.0 * c->ncomp * nqs * ne) + 8.0 * nd * ne +
                          (tile_dfold_ok(c) ? 16.0 * nl : 0.0);  // CG apply with the direction fold:
                                                                 // + d_old gather, + d store
             else             // x gather (each L-dof once) + qdata stream + element map + E-vector write
                              // (pa_geom: the element's mask and 21 map coefficients instead of its stream)
                 *bytes = 8.0 * nl + (c->qlay == 0 && c->dim == 3 && pa_geom_on(c) ? 8.0 * GeomLayout::kNC * ne
+                                     : hgeo                                       ? 8.0 * HoGeomLayout::kNC * ne
                                                                                   : 8.0 * c->ncomp * nqs * ne) +
                          4.0 * nd * ne + 8.0 * nd * ne;
             break;

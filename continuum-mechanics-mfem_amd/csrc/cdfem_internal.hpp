@@ -311,6 +311,10 @@ struct cdfem_ctx {
                                         // element's trilinear map (AF 3) instead of streaming it; read by
                                         // cdfem_pa_setup, 0 afterwards switches back to the stream
     double *d_geom = nullptr;           // pa_geom: header + [nblk][22][64] masks and map coefficients (GeomLayout)
+    int ho_geom = 0;                    // set_option "ho_geom": the same for the 3D p = 3, 4 tile apply where it runs
+                                        // the stream (MF & 32 of k_apply3d_tile); read by cdfem_pa_setup, 0
+                                        // afterwards switches back to the stream
+    double *d_hgeom = nullptr;          // ho_geom: GeomLayout's header + [ne][24] map coefficients (HoGeomLayout)
     double *d_Ye = nullptr;             // [nblk][nd][64]
     double *d_dinv = nullptr;           // Jacobi (constrained: ess -> 1)
     bool dinv_ready = false;
@@ -370,6 +374,12 @@ inline bool tile_kron(const cdfem_ctx *c) { return c->d_qaff != nullptr && c->ho
 inline int pa_af(const cdfem_ctx *c) { return c->d_qaff == nullptr ? 0 : (c->pa_affine == 2 ? 2 : 1); }
 // pa_geom taken by the setup and still on: the 3D p <= 2 applies run the AF 3 core on d_geom
 inline bool pa_geom_on(const cdfem_ctx *c) { return c->d_geom != nullptr && c->pa_geom != 0 && c->d_qaff == nullptr; }
+// ho_geom taken by the setup and still on: the p = 3, 4 tile apply forms the point data from d_hgeom
+// wherever it would run the stream (not the affine forms, not the matrix-core stage variants)
+inline bool ho_geom_on(const cdfem_ctx *c)
+{
+    return c->d_hgeom != nullptr && c->ho_geom != 0 && c->d_qaff == nullptr && c->ho_mfma == 0;
+}
 // the form the 3D p <= 2 apply kernels are launched with (their AF argument): pa_af, or 3 under pa_geom.
 // Everything else that asks for the form (folds, patch buffers, accounting of the other kernels) asks
 // pa_af: AF 3 runs wherever the stream (AF 0) does, with the same launch structure.
@@ -384,6 +394,8 @@ hipError_t launch_setup_qdata(cdfem_ctx *c, const double *d_kappa_q, const doubl
                               double mass);
 // pa_geom: fills d_geom's blocks from the vertices (the header is the caller's)
 hipError_t launch_setup_geom(cdfem_ctx *c);
+// ho_geom: fills d_hgeom's elements from the vertices (the header is the caller's)
+hipError_t launch_setup_hgeom(cdfem_ctx *c);
 hipError_t launch_apply(cdfem_ctx *c, const double *x, double *Ye, bool constrained);
 hipError_t launch_apply_wpe(cdfem_ctx *c, const double *x, double *Ye, bool con, const KrylovState *st);
 hipError_t launch_apply_st(cdfem_ctx *c, const double *x, double *Ye, bool constrained,

@@ -26,6 +26,11 @@
 // whole element's qdata (Q1 planes) is issued at kernel entry, in flight behind the gather and the
 // x / y stages.  Streaming (non-temporal) loads keep the L-vector in L2 for the gathers.
 //
+// Geometry mode (set_option "ho_geom", off by default; MF & 32): on a hex mesh the affine forms do not take,
+// with constant coefficients, qd is the element-major geometry array (pa_core.hpp HoGeomLayout: 24 doubles
+// per element) and every thread forms its points' operator from the trilinear map, plane by plane, as
+// elem_apply3d<..., GEO> does: no qdata stream, 96-154 VGPRs, three waves per SIMD.
+//
 // MFMA (set_option "ho_mfma", off by default): the four LDS stages also exist as block-wide GEMMs
 // on v_mfma_f64_16x16x4_f64 (block_mfma below).  On gfx950 the f64 MFMA rate is ~1.2x the f64
 // vector FMA rate and these contractions fill at most half of a 16x16x4 tile; the kernel is
@@ -69,8 +74,10 @@ k_apply3d_tile(const int32_t *__restrict__ map, const double *__restrict__ x, co
                const KrylovState *__restrict__ st, double *__restrict__ part)
 {
     static_assert(!DEN || (CON && LAT), "den partials need the constrained lattice path");
+    static_assert((MF & 32) == 0 || MF == 32, "the geometry form excludes the affine factors and the MFMA stages");
     if (st != nullptr && st->done) return;
     using L = QLayout<K, 3>;
+    constexpr bool GEO = (MF & 32) != 0;
     constexpr int NC = L::nc, NP = NC / 2, QQ = Q1 * Q1, ND = D1 * D1 * D1;
     constexpr int PS = qd_ho_plane(NC, Q1);  // doubles per (element, plane) block
     constexpr int EPB = 256 / QQ;            // elements per block
@@ -129,8 +136,23 @@ k_apply3d_tile(const int32_t *__restrict__ map, const double *__restrict__ x, co
     // this thread's qdata, all planes, in flight from here on (the scheduling barrier keeps the
     // gather loads ahead of the stream in issue order)
     __builtin_amdgcn_sched_barrier(0);
-    double qv[Q1][NC];
-    if constexpr ((MF & 16) != 0) {
+    double qv[GEO ? 1 : Q1][GEO ? 1 : NC];
+    // GEO (ho_geom): qd holds GeomLayout's header and then [e][HoGeomLayout::kNC], the coefficients a1..a7 of
+    // the element's trilinear map (every thread of a tile reads the same 11 x 16 bytes), and this thread's
+    // reference coordinates xi = point[tx], eta = point[ty].  A clamped thread reads element ne - 1, a real
+    // element (det J != 0); its results are discarded.
+    double ga[GEO ? 22 : 1], gxi = 0.0, geta = 0.0;
+    if constexpr (GEO) {
+        const v2d_t *ge = reinterpret_cast<const v2d_t *>(qd + GeomLayout::kHdr + (size_t)ec * HoGeomLayout::kNC);
+#pragma unroll
+        for (int p = 0; p < 11; ++p) {
+            const v2d_t w = ge[p];
+            ga[2 * p] = w.x;
+            ga[2 * p + 1] = w.y;
+        }
+        gxi = qd[GeomLayout::hPts + tx];
+        geta = qd[GeomLayout::hPts + ty];
+    } else if constexpr ((MF & 16) != 0) {
         // affine factors (pa_affine): qd holds g[e][NC]; the point data W_q g_k with W_q = (w_x w_y) w_z,
         // the product the setup stores (k_setup_qdata), formed after the table barrier below
 #pragma unroll
@@ -169,6 +191,24 @@ k_apply3d_tile(const int32_t *__restrict__ map, const double *__restrict__ x, co
 #pragma unroll
             for (int k = 0; k < NC; ++k) qv[qz][k] = W * g[k];
         }
+    }
+    // GEO: the parts of J that are fixed along this thread's column of points (pa_core.hpp elem_apply3d,
+    // GEO: x = a0 + a1 xi + a2 eta + a3 zeta + a4 xi eta + a5 xi zeta + a6 eta zeta + a7 xi eta zeta):
+    //     dx/dxi   = (a1 + eta a4) + zeta (a5 + eta a7)         gp0 + zeta gp1
+    //     dx/deta  = (a2 + xi a4) + zeta (a6 + xi a7)           gq0 + zeta gq1
+    //     dx/dzeta = (a3 + eta a6) + xi (a5 + eta a7)           gc2, constant along the column
+    // and w_x w_y; 15 doubles against the stream's Q1 * NC
+    double gp0[3] = {}, gp1[3] = {}, gq0[3] = {}, gq1[3] = {}, gc2[3] = {}, gwxy = 0.0;
+    if constexpr (GEO) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            gp0[i] = ga[0 + i] + geta * ga[9 + i];
+            gp1[i] = ga[12 + i] + geta * ga[18 + i];
+            gq0[i] = ga[3 + i] + gxi * ga[9 + i];
+            gq1[i] = ga[15 + i] + gxi * ga[18 + i];
+            gc2[i] = (ga[6 + i] + geta * ga[15 + i]) + gxi * gp1[i];
+        }
+        gwxy = sW[tx] * sW[ty];
     }
     // stage x: threads (qx = tx, dy = ty), or the matrix cores (MF & 1)
     constexpr int DD = D1 * D1, DQ = D1 * Q1;
@@ -268,6 +308,17 @@ k_apply3d_tile(const int32_t *__restrict__ map, const double *__restrict__ x, co
     for (int dz = 0; dz < D1; ++dz) w0[dz] = wx[dz] = wy[dz] = 0.0;
 #pragma unroll
     for (int qz = 0; qz < Q1; ++qz) {
+        // GEO: the planes one after another.  A plane's geometry depends on nothing else in the loop, and
+        // left alone the compiler forms adj J and det J of all Q1 planes ahead of it and defers the
+        // accumulations (Q1 * 13 doubles live at once; 201-240 VGPRs, or spills under a bound).  The empty
+        // asm statements keep their order: zeta and the column's inputs pass through one at the head of
+        // the plane, the accumulators through one each at its end.
+        double zeta = 0.0;
+        if constexpr (GEO) {
+            zeta = qd[GeomLayout::hPts + qz];
+            if constexpr (L::kD || L::kC) asm volatile("" : "+v"(zeta), "+v"(bb[0]), "+v"(bg[0]), "+v"(gb[0]));
+            else asm volatile("" : "+v"(zeta), "+v"(bb[0]));
+        }
         double u = 0.0, ux = 0.0, uy = 0.0, uz = 0.0;
 #pragma unroll
         for (int dz = 0; dz < D1; ++dz) {
@@ -278,21 +329,61 @@ k_apply3d_tile(const int32_t *__restrict__ map, const double *__restrict__ x, co
             uy += bz * gb[dz];
         }
         double v0 = 0.0, vx = 0.0, vy = 0.0, vz = 0.0;
-        if constexpr (L::kD) {
-            const double d00 = qv[qz][0], d01 = qv[qz][1], d02 = qv[qz][2];
-            const double d11 = qv[qz][3], d12 = qv[qz][4], d22 = qv[qz][5];
-            vx = d00 * ux + d01 * uy + d02 * uz;
-            vy = d01 * ux + d11 * uy + d12 * uz;
-            vz = d02 * ux + d12 * uy + d22 * uz;
+        if constexpr (GEO) {
+            // the point operator in its factors, as elem_apply3d<..., GEO>: tg = adj(J)^T grad_ref u, then
+            // D grad_ref u = (W kappa / det J) adj(J) tg, C . grad_ref u = W (alpha c) . tg, M u = (W s det J) u
+            const double W = gwxy * T.w[qz];
+            double c0[3], c1[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                c0[i] = gp0[i] + zeta * gp1[i];
+                c1[i] = gq0[i] + zeta * gq1[i];
+            }
+            double Aj[3][3];  // adj(J): rows c1 x c2, c2 x c0, c0 x c1
+            cross3(c1, gc2, Aj[0]);
+            const double det = c0[0] * Aj[0][0] + c0[1] * Aj[0][1] + c0[2] * Aj[0][2];
+            double tg[3] = {0.0, 0.0, 0.0};
+            if constexpr (L::kD || L::kC) {
+                cross3(gc2, c0, Aj[1]);
+                cross3(c0, c1, Aj[2]);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) tg[k] = Aj[0][k] * ux + Aj[1][k] * uy + Aj[2][k] * uz;
+            }
+            if constexpr (L::kD) {
+                const double sd = W * qd[GeomLayout::hKappa] * rcp_nr(det);
+                const double s0 = sd * tg[0], s1 = sd * tg[1], s2 = sd * tg[2];
+                vx = Aj[0][0] * s0 + Aj[0][1] * s1 + Aj[0][2] * s2;
+                vy = Aj[1][0] * s0 + Aj[1][1] * s1 + Aj[1][2] * s2;
+                vz = Aj[2][0] * s0 + Aj[2][1] * s1 + Aj[2][2] * s2;
+            }
+            if constexpr (L::kC)
+                v0 = W * (qd[GeomLayout::hConv] * tg[0] + qd[GeomLayout::hConv + 1] * tg[1] +
+                          qd[GeomLayout::hConv + 2] * tg[2]);
+            if constexpr (L::kM) v0 += (W * qd[GeomLayout::hMass] * det) * u;
+        } else {
+            if constexpr (L::kD) {
+                const double d00 = qv[qz][0], d01 = qv[qz][1], d02 = qv[qz][2];
+                const double d11 = qv[qz][3], d12 = qv[qz][4], d22 = qv[qz][5];
+                vx = d00 * ux + d01 * uy + d02 * uz;
+                vy = d01 * ux + d11 * uy + d12 * uz;
+                vz = d02 * ux + d12 * uy + d22 * uz;
+            }
+            if constexpr (L::kC) v0 += qv[qz][L::oC] * ux + qv[qz][L::oC + 1] * uy + qv[qz][L::oC + 2] * uz;
+            if constexpr (L::kM) v0 += qv[qz][L::oM] * u;
         }
-        if constexpr (L::kC) v0 += qv[qz][L::oC] * ux + qv[qz][L::oC + 1] * uy + qv[qz][L::oC + 2] * uz;
-        if constexpr (L::kM) v0 += qv[qz][L::oM] * u;
 #pragma unroll
         for (int dz = 0; dz < D1; ++dz) {
             const double bz = T.B[qz][dz], gz = T.G[qz][dz];
             w0[dz] += bz * v0 + gz * vz;
             wx[dz] += bz * vx;
             wy[dz] += bz * vy;
+        }
+        if constexpr (GEO) {
+#pragma unroll
+            for (int dz = 0; dz < D1; ++dz) {
+                asm volatile("" : "+v"(w0[dz]));
+                if constexpr (L::kD) asm volatile("" : "+v"(wx[dz]), "+v"(wy[dz]));
+            }
         }
     }
     // X (bufA) was last read in stage x, before the previous barrier
@@ -689,7 +780,8 @@ static hipError_t tile_kinds_mf(cdfem_ctx *c, const double *x, double *Ye, bool 
     geo.Ly = (uint32_t)c->Ly;
     geo.nz = c->epencil ? (uint32_t)(c->ne / ((int64_t)geo.ho.nx * geo.ho.ny)) : 0;
     geo.ess = c->d_ess;
-    const double *qd = (MF & 16) ? c->d_qaff : c->d_qd;
+    const double *qd = (MF & 32) ? c->d_hgeom : (MF & 16) ? c->d_qaff : c->d_qd;
+    if (qd == nullptr) return hipErrorInvalidValue;
     if (den_part) {
         if (!c->epencil || !con) return hipErrorInvalidValue;
         CDFEM_LAUNCH(c, (k_apply3d_tile<D1, Q1, K, true, true, true, MF>), grid, block, 0, c->d_map, x, qd,
@@ -730,6 +822,8 @@ static hipError_t tile_kinds(cdfem_ctx *c, const double *x, double *Ye, bool con
         }
         return tile_kinds_mf<D1, Q1, K, 16>(c, x, Ye, con, st, den_part);
     }
+    // geometric factors formed in the apply (ho_geom: any hex, constant coefficients, ho_mfma 0)
+    if (ho_geom_on(c)) return tile_kinds_mf<D1, Q1, K, 32>(c, x, Ye, con, st, den_part);
     switch (c->ho_mfma) {
     case 1: return tile_kinds_mf<D1, Q1, K, 1>(c, x, Ye, con, st, den_part);
     case 3: return tile_kinds_mf<D1, Q1, K, 3>(c, x, Ye, con, st, den_part);

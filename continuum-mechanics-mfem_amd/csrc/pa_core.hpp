@@ -159,6 +159,14 @@ struct GeomLayout {
     static constexpr int oLive = 0, oA = 1;  // a_m component i at oA + 3 (m - 1) + i
 };
 
+// ho_geom (cdfem_ctx::d_hgeom): the same for the high-order tile apply (qlay 1).  GeomLayout's header,
+// then element-major [ne][kNC]: a_m component i at 3 (m - 1) + i, 21 coefficients and 3 zeros, so every
+// element starts on a 64-byte boundary and is read with 16-byte loads.  No padding lane, no mask: elements
+// are addressed directly.  8 * 24 = 192 B per element against the stream's 8 NQ NC.
+struct HoGeomLayout {
+    static constexpr int kNC = 24;
+};
+
 // doubles per element block of what an apply reads through qd, by form (AF 0 stream, 1 / 2 affine
 // factors, 3 geometry), and the block's first double
 template <int Q1, unsigned K, int AF>

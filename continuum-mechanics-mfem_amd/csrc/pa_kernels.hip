@@ -384,6 +384,32 @@ k_setup_geom(const double *__restrict__ verts, const int32_t *__restrict__ perm,
     }
 }
 
+// ho_geom: the same coefficients (the same differences in the same order, so the two layouts hold the
+// same values for the same element) element-major for the high-order tile apply (pa_core.hpp
+// HoGeomLayout), thread per element
+__global__ void __launch_bounds__(256)
+k_setup_hgeom(const double *__restrict__ verts, int ne, double *__restrict__ geom)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ne) return;
+    double *out = geom + GeomLayout::kHdr + (size_t)e * HoGeomLayout::kNC;
+    const double *V = verts + (size_t)e * 24;
+    for (int i = 0; i < 3; ++i) {
+        const double v0 = V[i], v1 = V[3 + i], v2 = V[6 + i], v3 = V[9 + i];
+        const double v4 = V[12 + i], v5 = V[15 + i], v6 = V[18 + i], v7 = V[21 + i];
+        double a[7];
+        a[0] = v1 - v0;
+        a[1] = v2 - v0;
+        a[2] = v4 - v0;
+        a[3] = (v3 - v2) - (v1 - v0);
+        a[4] = (v5 - v4) - (v1 - v0);
+        a[5] = (v6 - v4) - (v2 - v0);
+        a[6] = ((v7 - v6) - (v5 - v4)) - ((v3 - v2) - (v1 - v0));
+        for (int m = 0; m < 7; ++m) out[3 * m + i] = a[m];
+        out[21 + i] = 0.0;
+    }
+}
+
 // physical coordinates of rule points: xyz[(e*nq + q)*dim + k]
 template <int DIM>
 __global__ void k_quad_points(const double *__restrict__ verts, int ne, const Rule1D r,
@@ -770,6 +796,13 @@ hipError_t launch_setup_geom(cdfem_ctx *c)
     const int64_t n = (int64_t)c->nblk * kLanes;
     hipLaunchKernelGGL(k_setup_geom, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, c->d_verts, c->d_perm, c->ne,
                        c->nblk, c->d_geom);
+    return hipGetLastError();
+}
+
+hipError_t launch_setup_hgeom(cdfem_ctx *c)
+{
+    hipLaunchKernelGGL(k_setup_hgeom, dim3(grid_for(c->ne, 256)), dim3(256), 0, c->stream, c->d_verts, (int)c->ne,
+                       c->d_hgeom);
     return hipGetLastError();
 }
 

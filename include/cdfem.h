@@ -371,7 +371,36 @@ int cdfem_fp64_bench(cdfem_ctx *ctx, int mode, int reps, double *tflops);
  *              5.98e9; apply bytes 140.9 MB against 1,436.9 MB, flops 3.12 G against 1.85 G (32.7 TFLOP/s,
  *              0.42 of the f64 peak: the apply is VALU-bound).  Kinds 5: apply 92.9 against 178.1 us, CG
  *              1.43e10 against 9.04e9.  Iterates agree to 3e-15.  Not measured: the generic element-block
- *              apply, p = 1, several ranks (parity-tested only), and no counter pass was taken.
+ *              apply, p = 1, several ranks (parity-tested only), and no counter pass was taken.  The p = 3, 4
+ *              tile apply has its own option of the same kind, "ho_geom".
+ * "ho_geom": 0 (default) or 1 — read by cdfem_pa_setup: the same for the high-order tile apply.  With 1 the
+ *              setup keeps, next to the per-point stream, 24 doubles per element, element-major (the
+ *              coefficients a1..a7 of the trilinear map, the same values pa_geom keeps, and 3 zeros: 192 B
+ *              against the stream's 17,280 B at p = 4, kinds 7), and k_apply3d_tile (mode bit 32) forms the
+ *              point operator itself: thread (qx, qy) hoists the parts of J that are fixed along its column of
+ *              points (15 doubles and w_x w_y instead of the stream's Q1 * nc) and per plane qz forms the two
+ *              remaining columns of J, adj(J), det J and applies D, C, M in their factors exactly as
+ *              pa_core.hpp elem_apply3d<..., GEO> (the operator of the stream to rounding, one reciprocal per
+ *              point).  Taken when all of these hold: hex mesh, dim 3, p = 3 or 4 on the operators' rule
+ *              (q1 = p + 2); every coefficient constant (kappa_q, kappa_mat_q, conv_q and mass_q all NULL); the
+ *              affine forms not taken (mesh not affine, or "pa_affine" 0); "ho_mfma" 0 (read when the apply
+ *              runs: the matrix-core stage variants keep the stream).  Every other case (p <= 2, 2D, per-point
+ *              coefficients, an affine mesh under pa_affine != 0) keeps its form without a word.  Mult, GMRES,
+ *              the fused and the unfused CG, generic meshes (the map gather), slabs and the general partition
+ *              take it wherever they run the stream tile; the launch structure is the stream's.  The stream is
+ *              still allocated and filled (the diagonal, FormLinearSystem and the linear form read it), so 0
+ *              after a setup switches back without a new setup; 1 needs one.  126-154 registers at kinds 7
+ *              (three waves per SIMD against the stream's two at 226-241), no scratch; a __launch_bounds__
+ *              (256, 3) gives the same register counts, so there was nothing to A/B.  The MFEM-shaped C++ layer
+ *              keeps the default.
+ *              Measured on the perturbed C3 box (128^3, p = 4, perturb 0.1, 135.0 M dofs; tools/ab_geom.py
+ *              --option ho_geom --p 4, DESIGN.md 4.2, profiles/r09/ab_c3_ho_geom/), ho_geom 1 against 0 on the
+ *              same box in one process, kinds 7: apply 4,176 against 7,123 us, CG 1.98e10 against 1.40e10
+ *              DoF-iter/s, GMRES(30) 1.09e10 against 8.52e9; apply bytes 3.71 GB against 39.55 GB, flops 115.5 G
+ *              against 81.4 G (27.7 TFLOP/s, 0.35 of the f64 peak: the apply has left the HBM bound).  Kinds 5:
+ *              apply 4,128 against 5,701 us, CG 2.00e10 against 1.65e10.  Iterates agree to 4.0e-15.  On 64^3:
+ *              apply 530.9 against 897.1 us, CG 1.96e10 against 1.37e10.  Not measured: p = 3, the generic (map
+ *              gather) path, several ranks (parity-tested only), and no counter pass was taken.
  * "cg_xfold": 1 (default) — structured brick CG (p <= 2, Kronecker form): each apply after the first
  *             advances x by the previous iteration's alpha d on the dofs it writes the new direction
  *             for, so the update kernel streams neither x nor d (bitwise the same iterates; 1 % faster
@@ -432,11 +461,11 @@ int cdfem_profile_launches(cdfem_ctx *ctx, int kernel, double *ms, int64_t cap, 
 /* algorithmic bytes moved by one launch of kernel id (see DESIGN.md for the per-unit figures); on
  * structured boxes the figure is that of the kernel the CG solve launches (the brick CG kernels, the
  * fused high-order apply with its direction fold); under pa_geom the apply's 176 B of geometry per
- * element replace the per-point stream's 8 nq nc                                                   */
+ * element (under ho_geom 192 B) replace the per-point stream's 8 nq nc                             */
 int cdfem_kernel_bytes(cdfem_ctx *ctx, int kernel, double *bytes);
 /* algorithmic f64 flops of one launch of the 3D partial-assembly apply (CDFEM_K_APPLY; FMA = 2):
  * the sum-factorized element apply (plus the point data W_q * g_e under pa_affine 1, or the point
- * operator formed from the element's trilinear map under pa_geom, its reciprocal counted as 1), or
+ * operator formed from the element's trilinear map under pa_geom or ho_geom, its reciprocal counted as 1), or
  * the Kronecker-form element apply under pa_affine 2                             */
 int cdfem_kernel_flops(cdfem_ctx *ctx, int kernel, double *flops);
 /* the HIP kernel name (without template arguments) kernel id runs as in the current configuration,

@@ -1,12 +1,15 @@
 """Interleaved in-process A/B of the geometry-in-the-apply form (pa_geom 1: point data formed from the
 element's trilinear map, pa_core.hpp elem_apply3d<..., GEO>) against the per-point qdata stream
-(pa_geom 0) on a PERTURBED C2 box (64^3 hex p = 2, no element a parallelepiped), kinds 7 and 5.
+(pa_geom 0) on a PERTURBED C2 box (64^3 hex p = 2, no element a parallelepiped), kinds 7 and 5.  With
+--option ho_geom --p 4 (or 3) the same A/B of the high-order tile apply's geometry mode (k_apply3d_tile,
+mode bit 32) against its stream.
 
-Two contexts per kinds mask (pa_geom is read by pa_setup); per round each runs a fixed Jacobi-CG solve
+Two contexts per kinds mask (the option is read by pa_setup); per round each runs a fixed Jacobi-CG solve
 (apply launch time from the profiling events) and a fixed GMRES(30) solve.  Prints medians, the apply's
 bytes and flops, and the relative difference of the two contexts' iterates as one JSON record.
 
-    python tools/ab_geom.py [--rounds 5] [--iters 100] [--n 64] [--kinds 7,5] [--out record.json]
+    python tools/ab_geom.py [--option pa_geom] [--p 2] [--rounds 5] [--iters 100] [--n 64] [--kinds 7,5]
+                            [--out record.json]
 """
 import argparse
 import json
@@ -21,6 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, "continuum-mechanics-mfem_amd", "python"))
 import cdfem  # noqa: E402
 
 ap = argparse.ArgumentParser()
+ap.add_argument("--option", default="pa_geom", choices=["pa_geom", "ho_geom"])
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--iters", type=int, default=100)
 ap.add_argument("--gmres-iters", type=int, default=60)
@@ -44,11 +48,12 @@ def one_pass(kinds):
     runs = []
     for geom in (1, 0):
         ctx = cdfem.Context(0)
-        ctx.set_option("pa_geom", geom)
+        ctx.set_option(args.option, geom)
         ctx.upload_mesh(mesh).set_structured(n, n, n)
         ctx.pa_setup(kinds=kinds, kappa=0.1, conv=(1.0, -2.0, 0.5), mass=1.0)
         _, B = ctx.form_linear_system(np.zeros(mesh.nl), b)
-        runs.append(dict(label=f"pa_geom={geom}", ctx=ctx, dB=ctx.to_device(B), dX=ctx.alloc(8 * mesh.nl),
+        runs.append(dict(label=f"{args.option}={geom}", name=ctx.kernel_name(cdfem.K_APPLY), ctx=ctx,
+                         dB=ctx.to_device(B), dX=ctx.alloc(8 * mesh.nl),
                          bytes=ctx.kernel_bytes(cdfem.K_APPLY), flops=ctx.kernel_flops(cdfem.K_APPLY),
                          cg_us=[], apply_us=[], upd_us=[], gm_us=[]))
     for rnd in range(args.rounds + 1):  # (round 0 warms up)
@@ -82,6 +87,7 @@ def one_pass(kinds):
     for r in runs:
         med = {k: float(np.median(r[k])) for k in ("cg_us", "apply_us", "upd_us", "gm_us")}
         med["apply_us_min"] = float(np.min(r["apply_us"]))
+        med["apply_kernel"] = r["name"]
         med["apply_bytes"] = r["bytes"]
         med["apply_flops"] = r["flops"]
         med["apply_gb_per_s"] = r["bytes"] / (med["apply_us"] * 1e-6) / 1e9
@@ -93,8 +99,8 @@ def one_pass(kinds):
     return out
 
 
-rec = {"shape": [n, n, n], "p": args.p, "perturb": args.perturb, "dofs": mesh.nl, "rounds": args.rounds,
-       "cg_iters": args.iters, "gmres_iters": args.gmres_iters}
+rec = {"option": args.option, "shape": [n, n, n], "p": args.p, "perturb": args.perturb, "dofs": mesh.nl,
+       "rounds": args.rounds, "cg_iters": args.iters, "gmres_iters": args.gmres_iters}
 for k in [int(s) for s in args.kinds.split(",")]:
     rec[f"kinds={k}"] = one_pass(k)
 text = json.dumps(rec, indent=1)
