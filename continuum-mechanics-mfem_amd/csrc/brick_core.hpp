@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "pa_core.hpp"
 
@@ -77,6 +78,54 @@ struct PatchWalk {
     }
 };
 
+// workgroup b runs on XCD b % 8; with xcd = 1 each XCD takes a contiguous range of bricks, so a
+// brick's neighbours (which re-read its patch faces) are mostly on the same L2.  Measured in
+// process (tools/ab.py, 64^3 p=2, two boxes): 242.8 vs 258.6 us per k_brick_cg launch; at 256^3
+// no difference (14444 vs 14470 us).
+__device__ __forceinline__ int brick_id(const BrickGeom &g)
+{
+    if (!g.xcd) return blockIdx.x;
+    const unsigned G = gridDim.x, b = blockIdx.x, x = b % 8, k = b / 8, q = G / 8, r = G % 8;
+    return (int)(x * q + (x < r ? x : r) + k);
+}
+
+// PatchWalk plus the lattice index gid = gx + Lx gy + Lxy gz of the position, advanced with the walk's
+// carries (no per-position 32-bit multiplies: v_mul_lo_u32 issues at a quarter of the VALU rate)
+template <int S, int STEP = 64>
+struct LatWalk {
+    int x, y, z;
+    uint32_t gid;
+    __device__ __forceinline__ LatWalk(unsigned t, uint32_t g0, uint32_t Lx, uint32_t Lxy)
+        : x((int)(t % S)), y((int)((t / S) % S)), z((int)(t / (S * S)))
+    {
+        gid = g0 + (uint32_t)x + Lx * (uint32_t)y + Lxy * (uint32_t)z;
+    }
+    __device__ __forceinline__ void next(uint32_t dgid, uint32_t cxd, uint32_t cyd)
+    {
+        constexpr int dx = STEP % S, dy = (STEP / S) % S, dz = STEP / (S * S);
+        x += dx;
+        const int cx = x >= S ? 1 : 0;
+        x -= S & -cx;
+        y += dy + cx;
+        const int cy = y >= S ? 1 : 0;
+        y -= S & -cy;
+        z += dz + cy;
+        // dgid = dx + dy Lx + dz Lxy; a carry out of x adds Lx - S, out of y Lxy - S Lx
+        gid += dgid + (cxd & (uint32_t)-cx) + (cyd & (uint32_t)-cy);
+    }
+};
+
+// f(std::integral_constant<int, k>) for k = B .. E - 1, unrolled at compile time (array indices
+// stay compile-time, so the arrays stay in registers)
+template <int B, int E, typename F>
+__device__ __forceinline__ void static_for(F &&f)
+{
+    if constexpr (B < E) {
+        f(std::integral_constant<int, B>{});
+        static_for<B + 1, E>(f);
+    }
+}
+
 // v unchanged, but opaque to the optimiser: index arithmetic that depends on it cannot be hoisted
 // above this point (LLVM otherwise computes a later phase's per-position indices at kernel entry
 // and spills them across the element apply)
@@ -129,6 +178,14 @@ __device__ __forceinline__ double patch_sum8(__amdgpu_buffer_rsrc_t bp, const Br
 // by the block CG's launcher in place of k_hobrick_cg when ho_uniform_elem(c)
 hipError_t launch_hobrick_um(cdfem_ctx *c, const BrickGeom &g, const double *r, const double *dinv, const double *d_old,
                              double *d_new, double *x);
+
+// pa_uniform: the p = 2 brick CG apply with the common element matrix (brick_um.hip k_brick_cg<XF, BF, FULL>),
+// launched by brick_cg2_launch in place of the Kronecker-form k_brick_cg when uniform_elem(c): nbrick_launch
+// bricks of the layers g.bz0, g.bz0 + g.bzs, ... on stream s (whole: the whole box on the context stream, with
+// the profiling events); kk >= 0: the betanom-fold apply after kk updates, with the update's nupart partials
+hipError_t launch_brick_um(cdfem_ctx *c, const BrickGeom &g, unsigned nbrick_launch, hipStream_t s, bool whole,
+                           const double *r, const double *dinv, const double *d_old, double *d_new, double *x, int kk,
+                           int nupart);
 
 // GMRES on the structured Mult (set_option "gm_pb"): A_c V_j is each row's 1-8 patch entries of the
 // patch-buffer Mult (k_brick3d<..., PBO>), V_j itself on the essential rows; pass 1 forms it there

@@ -1,0 +1,441 @@
+// brick_um.hip — pa_uniform: the p = 2 brick CG apply of a uniformly refined box with the common 27 x 27
+// element matrix as one GEMM on the matrix cores (k_brick_cg<XF, BF, FULL>, the overload of the Kronecker-form
+// kernel in brick_kernels.hip that brick_cg2_launch takes when uniform_elem(c)), the uniformity check and
+// the element matrix of the PA setup (setup_uniform_elem).  The update kernel it feeds is in
+// brick_kernels.hip (k_cg_update_faces).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "cdfem_internal.hpp"
+#include "brick_core.hpp"
+#include "pa_core.hpp"
+#include "reduce.hpp"
+
+// the E->L add of an accumulator into the output patch: 0 = explicit read, add, write (two z layers that
+// share no position per batch), 1 = one LDS f64 add without return per step.  A/B in
+// profiles/r10/ab_c2_brick_um/.
+#ifndef CDFEM_BUM_ADD
+#define CDFEM_BUM_ADD 0
+#endif
+
+namespace cdfem {
+
+// ---- the row order of the element matrix ---------------------------------------------------------
+// Accumulator register i of lane (n16, kg) in tile (mt, nt) is row slot 16 mt + 4 i + kg of element
+// (n16 & 3, n16 >> 2, nt).  An element's local dof (dx, dy, dz) lands on patch position 2 e + d per axis,
+// so two (element, dof) pairs meet on one position only if their dofs agree mod 2 per axis: the 27 dofs
+// fall into 8 parity classes of 8 (the corners), 4, 4, 4, 2, 2, 2 and 1 dofs that never meet each other,
+// and one dof's 16 elements of a z layer land on 16 different positions.  The 32 slots are 8 groups
+// (mt, i) of 4; kUmRow puts one corner and at most three further dofs of pairwise different classes in a
+// group, so the 64 lanes of a step (mt, i, nt) add into 64 different positions with no barrier and no
+// atomics, and a position's summation order is the program order of the steps.  Slots (kg 0, kg 1) and
+// (kg 2, kg 3) pair an even dx + dy + dz with an odd one: the two rows of a 32-lane half then differ by an
+// odd number of doubles and do not add to the element origins' own 2-way bank overlap.
+// kUmRow[slot] = local dof dx + 3 dy + 9 dz, -1 in the 5 padding slots.
+constexpr int kUmSlots = 32, kUmN = 27;
+constexpr int kUmRow[kUmSlots] = {0,  1,  4,  3,  2,  7,  22, 5,  6,  19, 10, 21, 8,  25, 16, 23,
+                                  18, 9,  12, 13, 20, 11, 14, -1, 24, 15, -1, -1, 26, 17, -1, -1};
+constexpr int um_class(int l) { return (l % 3 & 1) | ((l / 3 % 3 & 1) << 1) | ((l / 9 & 1) << 2); }
+constexpr bool um_row_order_ok()
+{
+    int seen[kUmN] = {};
+    for (int g = 0; g < kUmSlots / 4; ++g) {
+        int cls = 0;
+        if (kUmRow[4 * g] < 0 || um_class(kUmRow[4 * g]) != 0) return false;  // a corner first
+        for (int k = 0; k < 4; ++k) {
+            const int l = kUmRow[4 * g + k];
+            if (l < 0) continue;
+            if (l >= kUmN || seen[l]++) return false;
+            if (cls & (1 << um_class(l))) return false;  // two dofs of one class in a group
+            cls |= 1 << um_class(l);
+        }
+    }
+    for (int l = 0; l < kUmN; ++l)
+        if (!seen[l]) return false;
+    return true;
+}
+static_assert(um_row_order_ok(), "kUmRow: every dof once, one class once per group of 4 slots");
+
+// offset of slot 4 g + kg's dof in an S = 9 patch (x fastest), -1 for a padding slot: a select over the
+// lane's kg of four compile-time constants
+template <int G>
+__device__ __forceinline__ int um_slot_off(int kg)
+{
+    constexpr int S = 9;
+    auto off = [](int l) constexpr { return l < 0 ? -1 : (l / 9) * S * S + (l / 3 % 3) * S + l % 3; };
+    constexpr int o0 = off(kUmRow[4 * G]), o1 = off(kUmRow[4 * G + 1]), o2 = off(kUmRow[4 * G + 2]),
+                  o3 = off(kUmRow[4 * G + 3]);
+    return kg == 0 ? o0 : kg == 1 ? o1 : kg == 2 ? o2 : o3;
+}
+template <int G>
+constexpr bool um_group_padded() { return kUmRow[4 * G + 1] < 0 || kUmRow[4 * G + 2] < 0 || kUmRow[4 * G + 3] < 0; }
+
+// ================================================================================================
+// The brick CG apply (the protocol of k_brick_cg in brick_kernels.hip: patch gather, d = M^{-1} r + beta
+// d_old written by the writer brick, x-fold, beta-fold, den partials, essential-row patch entries, the
+// patch buffer k_cg_update_faces reads) with the brick's 64 element applies as
+//   Y (27 x 64) = A_e (27 x 27) X (27 x 64),
+// 2 x 4 tiles of 16 x 16 over 7 k-steps of 4 = 56 v_mfma_f64_16x16x4_f64.  amat is A_e in operand order
+// with its rows in kUmRow's: [mt][ks][lane] = A_e[kUmRow[16 mt + (lane & 15)]][4 ks + (lane >> 4)], 0 in
+// the padding, 14 doubles per lane held for the whole kernel.  B (lane: input dof 4 ks + (lane >> 4) of
+// element 16 nt + (lane & 15)) comes straight from the LDS patch, 0 for an element of a partial brick
+// outside the box (its column of Y and its den terms are then exactly 0).  The den terms and the E->L
+// sum are taken in the accumulator layout (kUmRow above); LDS is the input and the output patch.
+// The k order (columns of A_e, B rows) is the dofs' own: consecutive dofs lie an odd number of doubles
+// apart (1, 7 or 61), so the two dofs of a 32-lane half already miss each other's banks and the reads
+// sit on the 2-way floor of the 16 element origins (2 ex + 18 ey doubles: 12 distinct bank pairs).
+// kinds 7 and 5 differ in A_e only.  FULL: every brick's patch lies inside the lattice.
+// ================================================================================================
+template <bool XF, bool BF, bool FULL>
+__global__ void __launch_bounds__(64, 2)
+k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const double *__restrict__ d_old,
+           double *__restrict__ d_new, double *__restrict__ face, const double *__restrict__ amat,
+           const uint8_t *__restrict__ ess, const BrickGeom g, int zlo_shared, double *__restrict__ part,
+           KrylovState *__restrict__ st, double *__restrict__ x, const double *__restrict__ upart, int nupart,
+           int kk, double *__restrict__ gsum, uint32_t *__restrict__ gcnt, int grp, int nbrick)
+{
+    constexpr int P = 2, S = kBrick * P + 1, S2 = S * S, S3 = S * S * S, NDE = kUmN;
+    static_assert(S == 9, "um_slot_off is written for the 9^3 patch");
+    __shared__ double s_in[S3];
+    __shared__ double s_out[S3];
+    if (st->done) return;
+    brick_stagger(g);
+    double beta = st->beta;
+    constexpr int NPL = 16;  // BF: partials per lane (nupart <= 64 NPL)
+    double pv[NPL];
+    if constexpr (BF) {
+        if (kk > 0) {  // (buffer loads: past nupart they read 0, no branch per load)
+            const auto bu = brsrc(upart, 8u * (uint32_t)nupart);
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) pv[i] = bload(bu, 8u * ((uint32_t)threadIdx.x + 64u * i));
+        }
+    }
+    const double alpha_prev = XF ? st->alpha : 0.0;
+    const int t = threadIdx.x;
+    // launch-local brick -> global brick (a launch covers every g.bzs-th layer from g.bz0)
+    const int bl = brick_id(g), nxy = g.nbx * g.nby;
+    const int bz = g.bz0 + (bl / nxy) * g.bzs;
+    const int b = bl % nxy + nxy * bz;
+    const int bx = b % g.nbx, by = (b / g.nbx) % g.nby;
+    const int gx0 = (S - 1) * bx, gy0 = (S - 1) * by, gz0 = (S - 1) * bz;
+    const bool lastx = bx == g.nbx - 1, lasty = by == g.nby - 1, lastz = bz == g.nbz - 1;
+    double den = 0.0;
+    // patch gather: every load is issued before any is consumed; out-of-lattice positions of partial
+    // bricks use kOOB (loads 0, stores dropped); per position the writer's byte offset and one bit of
+    // dbits for "writer, and its d^2 counts in den" (k_brick_cg of brick_kernels.hip)
+    constexpr int NI = (S3 + 63) / 64;
+    const int Lx = g.Lx, Lxy = g.Lx * g.Ly;
+    const uint32_t nl = (uint32_t)Lxy * (uint32_t)g.Lz;
+    const auto br = brsrc(r, 8u * nl), bm = brsrc(dinv, 8u * nl), bo = brsrc(d_old, 8u * nl);
+    const auto be = brsrc(ess, nl), bd = brsrc(d_new, 8u * nl), bxf = brsrc(x, XF ? 8u * nl : 0u);
+    double rv[NI], mv[NI], ov[NI], xv[NI];
+    uint32_t woffv[NI];
+    uint32_t dbits = 0, ebits = 0;
+    uint8_t ev[NI];
+    double dev[NI];  // the essential entries' d (each position is formed and stored by the same thread)
+    const uint32_t uLx = (uint32_t)Lx, uLxy = (uint32_t)Lxy;
+    constexpr uint32_t wdx = 64 % S, wdy = (64 / S) % S, wdz = 64 / (S * S);
+    const uint32_t dgid = wdx + wdy * uLx + wdz * uLxy, cxd = uLx - S, cyd = uLxy - S * uLx;
+    LatWalk<S> pw0(t, (uint32_t)gx0 + uLx * (uint32_t)gy0 + uLxy * (uint32_t)gz0, uLx, uLxy);
+    auto gather = [&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        const unsigned i = t + 64 * k;
+        const int px = pw0.x, py = pw0.y, pz = pw0.z;
+        const uint32_t gid = pw0.gid;
+        pw0.next(dgid, cxd, cyd);
+        const int gz = gz0 + pz;
+        const bool in = i < S3 && (FULL || (gx0 + px < g.Lx && gy0 + py < g.Ly && gz < g.Lz));
+        const uint32_t off = in ? 8u * gid : kOOB;
+        rv[k] = bload(br, off);
+        mv[k] = bload(bm, off);
+        ov[k] = bload(bo, off);
+        ev[k] = __builtin_amdgcn_raw_buffer_load_b8(be, in ? gid : kOOB, 0, 0);
+        const bool writer = in && (px < S - 1 || lastx) && (py < S - 1 || lasty) && (pz < S - 1 || lastz);
+        woffv[k] = writer ? off : kOOB;
+        dbits |= (uint32_t)(writer && !(zlo_shared && gz == 0)) << k;
+        if constexpr (XF) xv[k] = bload(bxf, woffv[k]);
+    };
+    auto form = [&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        const unsigned i = t + 64 * k;
+        if (k == NI - 1 && i >= S3) return;
+        const double dn = mv[k] * rv[k] + beta * ov[k];  // 0 outside the lattice
+        const bool e = ev[k] != 0;
+        bstore(bd, woffv[k], dn);
+        if constexpr (XF) bstore(bxf, woffv[k], xv[k] + alpha_prev * ov[k]);
+        den += (e && ((dbits >> k) & 1u)) ? dn * dn : 0.0;  // (A_c d)_i = d_i on ess dofs
+        s_in[i] = e ? 0.0 : dn;
+        s_out[i] = 0.0;
+        ebits |= (uint32_t)e << k;
+        dev[k] = ((dbits >> k) & 1u) ? dn : 0.0;
+    };
+    static_for<0, NI>(gather);
+    if constexpr (BF) {
+        if (kk > 0) {
+            double v = 0.0;
+#pragma unroll
+            for (int q = 0; q < NPL; ++q) v += pv[q];
+            const double B = wave_sum(v);
+            // cg_update_logic's decision (cg_stop_kind), taken identically by every workgroup at the
+            // host's update count kk; workgroup 0 records it at the same kk
+            const bool stop = cg_stop_kind(st, B, kk) != kCgGoOn;
+            if (b == 0 && t == 0) {  // (global brick 0: one launch records, also when a slab is split in two)
+#ifdef CDFEM_DEBUG
+                assert(st->iter == kk);
+#endif
+                cg_update_logic_at(st, B, kk);
+            }
+            if (stop) return;
+            beta = B / st->nom;
+        }
+    }
+    static_for<0, NI>(form);
+    __syncthreads();
+
+    {
+        const int n16 = t & 15, kg = t >> 4;
+        double av[2][7];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int ks = 0; ks < 7; ++ks) av[mt][ks] = amat[(mt * 7 + ks) * 64 + t];
+        // element 16 nt + n16 of the brick: (ex, ey, ez) = (n16 & 3, n16 >> 2, nt); in a partial brick the
+        // elements past the box (their far corner outside the lattice) take B = 0
+        const int ob0 = P * (n16 >> 2) * S + P * (n16 & 3);
+        const bool vxy = FULL || (gx0 + P * (n16 & 3) + P < g.Lx && gy0 + P * (n16 >> 2) + P < g.Ly);
+        auto node_off = [&](int j) { return (j / 9) * S2 + ((j / 3) % 3) * S + j % 3; };
+        v4d_t acc[2][4];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = v4d_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int ks = 0; ks < 7; ++ks) {
+            const int j = 4 * ks + kg;  // this lane's input dof (27 = the k padding: B = 0)
+            const int jo = node_off(j < NDE ? j : 0);
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                const bool ok = j < NDE && vxy && (FULL || gz0 + P * nt + P < g.Lz);
+                const double xin = s_in[P * nt * S2 + ob0 + jo];
+                const double bv = ok ? xin : 0.0;
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mt][ks], bv, acc[mt][nt], 0, 0, 0);
+            }
+        }
+        // den: sum over (dof, element) of X Y, and the E->L sum, both in the accumulator layout: group
+        // G = 4 mt + i, this lane's dof of it at patch offset so (-1: a padding slot, whose Y is 0)
+        static_for<0, 8>([&](auto gc) {
+            constexpr int G = decltype(gc)::value, mt = G / 4, i = G % 4;
+            constexpr bool PADG = um_group_padded<G>();
+            const int so = um_slot_off<G>(kg);
+            const bool live = !PADG || so >= 0;
+            const int o = ob0 + (PADG ? max(so, 0) : so);
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                const double xin = s_in[P * nt * S2 + o];
+                den += live ? xin * acc[mt][nt][i] : 0.0;
+            }
+            if (live) {
+#if CDFEM_BUM_ADD == 1
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt)
+                    (void)__hip_atomic_fetch_add(&s_out[P * nt * S2 + o], acc[mt][nt][i], __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+#else
+                // layers nt and nt + 2 share no position (z = 2 nt + dz): two reads in flight per batch
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    double *const p0 = &s_out[P * h * S2 + o], *const p1 = &s_out[P * (h + 2) * S2 + o];
+                    const double v0 = *p0, v1 = *p1;
+                    *p0 = v0 + acc[mt][h][i];
+                    *p1 = v1 + acc[mt][h + 2][i];
+                }
+#endif
+            }
+        });
+    }
+    __syncthreads();
+
+    // the brick's whole patch output (interior rows complete, face rows partial; the essential rows carry
+    // the writer's d) -> the patch buffer (patch_idx in 32-bit arithmetic: index = base + pz A + py R + px)
+    {
+        const uint32_t R = (uint32_t)g.nbx * S, A = (uint32_t)g.nby * S * R;
+        const uint32_t base = (uint32_t)bz * S * A + (uint32_t)by * S * R + (uint32_t)bx * S;
+        const auto bp = brsrc(face, 8u * (uint32_t)g.nbx * g.nby * g.nbz * S3);
+        const unsigned to = (unsigned)opaque(t);
+        PatchWalk<S> pw(to);
+#pragma unroll
+        for (int k = 0; k < NI; ++k) {
+            const unsigned i = to + 64 * k;
+            if (k == NI - 1 && i >= S3) break;
+            double v = s_out[i];
+            v = ((ebits >> k) & 1u) ? dev[k] : v;
+            bstore(bp, 8u * (base + (uint32_t)pw.z * A + (uint32_t)pw.y * R + (uint32_t)pw.x), v);
+            pw.next();
+        }
+    }
+    den = wave_sum(den);
+    if (grp <= 1) {
+        if (t == 0) part[b] = den;
+        return;
+    }
+    // grouped partials (den_grp > 1), as k_brick_cg of brick_kernels.hip: write-through partial, agent-scope
+    // arrival count, the group's last brick sums its partials by the fixed wave tree and resets the counter
+    const int gi = b / grp, g0 = gi * grp, gn = min(grp, nbrick - g0);
+    uint32_t prev = 0;
+    if (t == 0) {
+        __hip_atomic_store(&part[b], den, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        prev = __hip_atomic_fetch_add(&gcnt[gi], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    prev = (uint32_t)__shfl((int)prev, 0, 64);
+    if (prev != (uint32_t)(gn - 1)) return;
+    double v = t < gn ? __hip_atomic_load(&part[g0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+    v = wave_sum(v);
+    if (t == 0) {
+        gsum[gi] = v;
+        __hip_atomic_store(&gcnt[gi], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+hipError_t launch_brick_um(cdfem_ctx *c, const BrickGeom &g, unsigned nbrick_launch, hipStream_t s, bool whole,
+                           const double *r, const double *dinv, const double *d_old, double *d_new, double *x, int kk,
+                           int nupart)
+{
+    if (c->d_uelem == nullptr || c->p != 2) return hipErrorInvalidValue;
+    const dim3 grid(nbrick_launch), block(64);
+    const double *upart = c->d_part + c->nblk;                  // the den-fold update's partials
+    double *const dpart = c->den_out ? c->den_out : c->d_part;  // the apply's den partials
+    const bool full = c->sx % kBrick == 0 && c->sy % kBrick == 0 && c->sz % kBrick == 0;
+#define CDFEM_BUM(XF_, BF_, FU_)                                                                              \
+    do {                                                                                                      \
+        if (whole)                                                                                            \
+            CDFEM_LAUNCH(c, (k_brick_cg<XF_, BF_, FU_>), grid, block, 0, r, dinv, d_old, d_new, c->d_face,      \
+                         c->d_uelem, c->d_ess, g, c->zlo_shared, dpart, c->d_state, x, upart, nupart, kk,       \
+                         c->d_gsum, c->d_gcnt, c->den_grp, c->nblk);                                            \
+        else                                                                                                  \
+            hipLaunchKernelGGL((k_brick_cg<XF_, BF_, FU_>), grid, block, 0, s, r, dinv, d_old, d_new, c->d_face, \
+                               c->d_uelem, c->d_ess, g, c->zlo_shared, dpart, c->d_state, x, upart, nupart, kk, \
+                               c->d_gsum, c->d_gcnt, c->den_grp, c->nblk);                                      \
+    } while (0)
+#define CDFEM_BUM2(XF_, BF_)                                                                                  \
+    do {                                                                                                      \
+        if (full) CDFEM_BUM(XF_, BF_, true);                                                                  \
+        else CDFEM_BUM(XF_, BF_, false);                                                                      \
+    } while (0)
+    if (kk >= 0) {
+        if (x) CDFEM_BUM2(true, true);
+        else CDFEM_BUM2(false, true);
+    } else {
+        if (x) CDFEM_BUM2(true, false);
+        else CDFEM_BUM2(false, false);
+    }
+#undef CDFEM_BUM2
+#undef CDFEM_BUM
+    return hipGetLastError();
+}
+
+// ---- pa_uniform: the common element matrix of a uniformly refined box ----------------------------
+// Every element slot's factors against slot 0's (brick 0, lane 0: element (0, 0, 0)); any component
+// further than tol flags the box as not uniform (plain vector stores of the same value).
+__global__ void __launch_bounds__(256)
+k_uniform_check(const double *__restrict__ gaff, const int32_t *__restrict__ perm, int nslots, int nc, int ne,
+                double tol, int *__restrict__ bad)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nslots) return;
+    const int e = perm[s];
+    if (e < 0 || e >= ne) return;
+    const size_t b = (size_t)(s / kLanes), lane = (size_t)(s % kLanes);
+    bool diff = false;
+    for (int k = 0; k < nc; ++k) diff |= fabs(gaff[(b * nc + k) * kLanes + lane] - gaff[(size_t)k * kLanes]) > tol;
+    if (diff) *bad = 1;
+}
+
+// column j of the element matrix = the Kronecker core (what k_brick_cg<..., AF 2> applies) on the unit
+// vector e_j with element 0's factors: thread j writes A[i][j], row-major N x N
+template <int D1, int Q1, unsigned K>
+__global__ void __launch_bounds__(64)
+k_uniform_elem(const double *__restrict__ gaff, const Tab<D1, Q1> T, double *__restrict__ A)
+{
+    constexpr int N = D1 * D1 * D1;
+    const int j = threadIdx.x;
+    if (j >= N) return;
+    double g[QLayout<K, 3>::nc];
+    kron_load_g<K>(gaff, 0, g);
+    auto xl = [&](int z, int y, int x) { return (z * D1 + y) * D1 + x == j ? 1.0 : 0.0; };
+    double Y[D1][D1][D1];
+    kron_core<D1, Q1, K>(xl, g, T, Y);
+    for (int i = 0; i < N; ++i) A[i * N + j] = Y[i / (D1 * D1)][(i / D1) % D1][i % D1];
+}
+
+hipError_t setup_uniform_elem(cdfem_ctx *c)
+{
+    if (c->d_uelem) {
+        const hipError_t e = hipFree(c->d_uelem);
+        c->d_uelem = nullptr;
+        if (e != hipSuccess) return e;
+    }
+    if (!c->pa_uniform || !c->structured || c->qlay != 0 || c->dim != 3 || pa_af(c) != 2 || c->p != 2 ||
+        c->rule_op.q1 != 4 || c->ncomp < 1 || (c->kinds != 7 && c->kinds != 5))
+        return hipSuccess;
+    const int nc = c->ncomp;
+    std::vector<double> g0(nc);
+    hipError_t e = hipMemcpy2D(g0.data(), sizeof(double), c->d_qaff, kLanes * sizeof(double), sizeof(double), nc,
+                               hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    double gmax = 0.0;
+    for (double v : g0) gmax = std::max(gmax, std::fabs(v));
+    // one scratch allocation: the flag, then the N x N matrix
+    constexpr int N = kUmN;
+    void *scratch = nullptr;
+    if ((e = hipMalloc(&scratch, sizeof(double) * (N * N + 1))) != hipSuccess) return e;
+    int *bad = static_cast<int *>(scratch);
+    double *A = static_cast<double *>(scratch) + 1;
+    int hbad = 0;
+    const int nslots = c->nblk * kLanes;
+    e = hipMemsetAsync(bad, 0, sizeof(int), c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_uniform_check, dim3((nslots + 255) / 256), dim3(256), 0, c->stream, c->d_qaff, c->d_perm,
+                           nslots, nc, (int)c->ne, 1e-14 * gmax, bad);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    std::vector<double> h(N * N), op(2 * 7 * 64, 0.0);
+    if (e == hipSuccess && !hbad) {
+        const Tab<3, 4> T = make_tab<3, 4>(c->rule_op);
+        if (c->kinds == 7) hipLaunchKernelGGL((k_uniform_elem<3, 4, 7>), dim3(1), dim3(64), 0, c->stream, c->d_qaff, T, A);
+        else hipLaunchKernelGGL((k_uniform_elem<3, 4, 5>), dim3(1), dim3(64), 0, c->stream, c->d_qaff, T, A);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(h.data(), A, sizeof(double) * N * N, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    const hipError_t ef = hipFree(scratch);
+    if (e != hipSuccess) return e;
+    if (ef != hipSuccess) return ef;
+    if (hbad) return hipSuccess;  // not uniform: the Kronecker form
+    // the A operands of v_mfma_f64_16x16x4_f64 in lane order, rows in kUmRow's order:
+    // [mt][ks][lane] = A[kUmRow[16 mt + (lane & 15)]][4 ks + (lane >> 4)]
+    for (int mt = 0; mt < 2; ++mt)
+        for (int ks = 0; ks < 7; ++ks)
+            for (int l = 0; l < 64; ++l) {
+                const int i = kUmRow[16 * mt + (l & 15)], j = 4 * ks + (l >> 4);
+                op[(mt * 7 + ks) * 64 + l] = (i >= 0 && j < N) ? h[i * N + j] : 0.0;
+            }
+    void *d = nullptr;
+    if ((e = hipMalloc(&d, sizeof(double) * op.size())) != hipSuccess) return e;
+    e = hipMemcpy(d, op.data(), sizeof(double) * op.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return e;
+    }
+    c->d_uelem = static_cast<double *>(d);
+    return hipSuccess;
+}
+
+}  // namespace cdfem

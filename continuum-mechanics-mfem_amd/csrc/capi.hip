@@ -2092,7 +2092,7 @@ int cdfem_kernel_flops(cdfem_ctx *c, int k, double *flops)
         const int D = c->d1, Q = c->rule_op.q1;
         const bool kD = c->kinds & CDFEM_DIFFUSION, kC = c->kinds & CDFEM_CONVECTION, kM = c->kinds & CDFEM_MASS;
         if (c->qlay == 0 && uniform_elem(c) && use_brick(c)) {
-            // the common element matrix (k_brick_cg<..., MX 2>): nd^2 MACs per element (the MFMA tiles'
+            // the common element matrix (brick_um.hip k_brick_cg<XF, BF, FULL>): nd^2 MACs per element (the MFMA tiles'
             // zero padding, 56 x 1024 MACs per 64 elements against 64 x 729, is not counted)
             *flops = 2.0 * (double)c->nd * c->nd * (double)c->ne;
             return CDFEM_OK;

@@ -176,7 +176,7 @@ struct cdfem_ctx {
     int pa_uniform = 1;                 // set_option "pa_uniform": when every element's factors equal the first
                                         // element's (a uniformly refined box, what MFEM's MakeCartesian3D
                                         // gives), the p = 2 brick CG applies that element's 27 x 27 matrix on
-                                        // the matrix cores (k_brick_cg<..., MX 2>); 0 keeps the Kronecker form
+                                        // the matrix cores (brick_um.hip k_brick_cg<XF, BF, FULL>); 0 keeps the Kronecker form
     double *d_uelem = nullptr;          // pa_uniform: the common element matrix in MFMA A-operand order
     int ho_uniform = 0;                 // set_option "ho_uniform": the p = 3, 4 block CG (2 x 2 x 4 blocks) applies the
                                         // common N x N element matrix of a uniform box (N = 64, 125) as one GEMM on
