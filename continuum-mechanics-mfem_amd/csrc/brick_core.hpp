@@ -115,6 +115,11 @@ struct LatWalk {
     }
 };
 
+// pa_uniform_diag: the class of lattice coordinate g on an axis of L dofs of a uniform p = 2 box, which with
+// the other two axes' classes fixes the assembled diagonal: 0 shared by two elements, 1 element-interior,
+// 2 the first plane, 3 the last.  The table index is cx + 4 cy + 16 cz.
+__host__ __device__ __forceinline__ int udiag_class(int g, int L) { return g == 0 ? 2 : g == L - 1 ? 3 : g & 1; }
+
 // f(std::integral_constant<int, k>) for k = B .. E - 1, unrolled at compile time (array indices
 // stay compile-time, so the arrays stay in registers)
 template <int B, int E, typename F>

@@ -775,7 +775,10 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv,
 // napart) in one fixed order and takes MFEM's den step itself (workgroup 0 records it), so the
 // one-block den finalizer and its launch go away; the grid is a few hundred to a few thousand
 // workgroups (grid-stride loop) to keep the redundant sums small, and its partials go to part.
-template <int S, bool XF, bool PB = false, bool DS = false, bool EP = false, int SZ = S>
+// UD (pa_uniform_diag, a uniform p = 2 box): dinv is the 64-entry class table of the Jacobi scale, held in
+// LDS; a dof takes 1 if essential, else the entry of its lattice class (udiag_class per axis).  Both loops
+// take it, so that the apply and the update use the same scale whatever brick_upd_pb says.
+template <int S, bool XF, bool PB = false, bool DS = false, bool EP = false, int SZ = S, bool UD = false>
 __global__ void __launch_bounds__(kRedThreads)
 k_cg_update_faces(double *__restrict__ x, double *__restrict__ r, const double *__restrict__ d,
                   const double *__restrict__ dinv, const double *__restrict__ pb,
@@ -788,7 +791,11 @@ k_cg_update_faces(double *__restrict__ x, double *__restrict__ r, const double *
     constexpr int s1 = S - 1, sz1 = SZ - 1;
     constexpr uint32_t PV = (uint32_t)S * S * SZ;  // patch entries per brick / block
     __shared__ double sh[kRedThreads / 64 + 1];
+    __shared__ double s_tab[UD ? kUdiagN : 1];
+    static_assert(!UD || kRedThreads >= kUdiagN, "UD: one table entry per thread");
     if (st->done) return;
+    double tabv = 0.0;
+    if constexpr (UD) tabv = threadIdx.x < kUdiagN ? dinv[threadIdx.x] : 0.0;
     double alpha = 0.0;
     if constexpr (DS) {
         // (16 loads per thread in flight at once: the apply's 4096 partials in one round trip)
@@ -812,6 +819,10 @@ k_cg_update_faces(double *__restrict__ x, double *__restrict__ r, const double *
     const int n = g.Lx * g.Ly * g.Lz;
     const int plane = g.Lx * g.Ly;
     double acc = 0.0;
+    if constexpr (UD) {
+        if (threadIdx.x < kUdiagN) s_tab[threadIdx.x] = tabv;
+        __syncthreads();
+    }
     if constexpr (EP) {
         // the apply's essential-row patch entries (EP in k_brick_cg): q is the sum of the row's 1-8
         // entries everywhere (with the neighbour's plane sums on a slab), so the loop reads r, M^-1 and
@@ -826,7 +837,15 @@ k_cg_update_faces(double *__restrict__ x, double *__restrict__ r, const double *
             const int rem = gid - gz * plane;
             const int gy = (int)fdiv((uint32_t)rem, fdx);
             const int gx = rem - gy * g.Lx;
-            const double rold = r[gid], mi = dinv[gid];
+            const double rold = r[gid];
+            double mi;
+            if constexpr (UD) {
+                const bool is_ess = ess[gid] != 0;
+                const double tv = s_tab[udiag_class(gx, g.Lx) + 4 * udiag_class(gy, g.Ly) + 16 * udiag_class(gz, g.Lz)];
+                mi = is_ess ? 1.0 : tv;
+            } else {
+                mi = dinv[gid];
+            }
             const double xi = XF ? 0.0 : x[gid], di = XF ? 0.0 : d[gid];
             double qi = patch_sum8<S, SZ>(bp, g, gx, gy, gz);
             if (remote_lo && gz == 0) qi += remote_lo[rem];
@@ -847,7 +866,14 @@ k_cg_update_faces(double *__restrict__ x, double *__restrict__ r, const double *
             const bool is_ess = ess[gid] != 0;
             // XF: x was advanced by the apply (x-fold); d is then needed on essential rows only
             const double di = (!XF || is_ess) ? d[gid] : 0.0, xi = XF ? 0.0 : x[gid];
-            const double rold = r[gid], mi = dinv[gid];
+            const double rold = r[gid];
+            double mi;
+            if constexpr (UD) {
+                const double tv = s_tab[udiag_class(gx, g.Lx) + 4 * udiag_class(gy, g.Ly) + 16 * udiag_class(gz, g.Lz)];
+                mi = is_ess ? 1.0 : tv;
+            } else {
+                mi = dinv[gid];
+            }
             double qi;
             if constexpr (PB) {
                 qi = patch_sum8<S, SZ>(brsrc(pb, 8u * (uint32_t)g.nbx * g.nby * g.nbz * PV), g, gx, gy, gz);
@@ -1400,18 +1426,26 @@ hipError_t launch_cg_update_faces(cdfem_ctx *c, double *x, double *r, const doub
     // the apply's den partials the den fold sums: one per brick, or the group sums (den_grp > 1)
     const double *const apart = c->den_grp > 1 ? c->d_gsum : c->d_part;
     const int napart = c->den_grp > 1 ? den_parts(c) : c->nblk;
-#define CDFEM_UPD4(S_, XF_, PB_, DS_, EP_)                                                                 \
-    hipLaunchKernelGGL((k_cg_update_faces<S_, XF_, PB_, DS_, EP_, SZ_>), dim3(ugrid), dim3(kRedThreads), 0, c->stream, x, \
+#define CDFEM_UPD4(S_, XF_, PB_, DS_, EP_, UD_)                                                               \
+    hipLaunchKernelGGL((k_cg_update_faces<S_, XF_, PB_, DS_, EP_, SZ_, UD_>), dim3(ugrid), dim3(kRedThreads), 0, c->stream, x, \
                        r, d, dinv, c->d_face, c->d_ess, g, fdx, fdxy, c->zlo_shared, remote_lo, remote_hi, upart, \
                        c->d_state, (int)den_step, apart, napart)
-    // the apply's essential-row patch entries (k_brick_cg EP: the Kronecker form at p <= 2)
-    const bool ep = pa_af(c) == 2 && c->p <= 2;
-#define CDFEM_UPD3(S_, XF_, PB_, DS_)                                                                      \
-    if (ep && PB_) { CDFEM_UPD4(S_, XF_, PB_, DS_, PB_); } else { CDFEM_UPD4(S_, XF_, PB_, DS_, false); }
-#define CDFEM_UPD2(S_, XF_, PB_)                                                                           \
-    if (ds) { CDFEM_UPD3(S_, XF_, PB_, true); } else { CDFEM_UPD3(S_, XF_, PB_, false); }
     // predicated-load face sums: the patch buffer's byte offsets must fit 32 bits
     const bool pb = c->brick_upd_pb != 0 && brick_fits(c);
+    // the apply's essential-row patch entries (k_brick_cg EP: the Kronecker form at p <= 2)
+    const bool ep = pa_af(c) == 2 && c->p <= 2;
+    // pa_uniform_diag: the Jacobi scale from the class table (the p = 2 patch only: UD_ is false in every
+    // other instantiation; not under pc = none, whose dinv is the ones vector)
+    const bool ud = uniform_diag(c) && dinv == c->d_dinv && c->p == 2;
+    if (ud) dinv = c->d_udiag;
+#define CDFEM_UPD3(S_, XF_, PB_, DS_)                                                                      \
+    if (ep && PB_) {                                                                                       \
+        if (ud) { CDFEM_UPD4(S_, XF_, PB_, DS_, PB_, (S_ == 9 && SZ_ == 9)); }                             \
+        else { CDFEM_UPD4(S_, XF_, PB_, DS_, PB_, false); }                                                \
+    } else if (ud) { CDFEM_UPD4(S_, XF_, PB_, DS_, false, (S_ == 9 && SZ_ == 9)); }                        \
+    else { CDFEM_UPD4(S_, XF_, PB_, DS_, false, false); }
+#define CDFEM_UPD2(S_, XF_, PB_)                                                                           \
+    if (ds) { CDFEM_UPD3(S_, XF_, PB_, true); } else { CDFEM_UPD3(S_, XF_, PB_, false); }
 #define CDFEM_UPD(S_)                                                                                       \
     if (xfold) {                                                                                            \
         if (pb) { CDFEM_UPD2(S_, true, true); } else { CDFEM_UPD2(S_, true, false); }                       \

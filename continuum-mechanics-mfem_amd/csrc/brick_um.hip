@@ -1,7 +1,8 @@
 // brick_um.hip — pa_uniform: the p = 2 brick CG apply of a uniformly refined box with the common 27 x 27
-// element matrix as one GEMM on the matrix cores (k_brick_cg<XF, BF, FULL>, the overload of the Kronecker-form
+// element matrix as one GEMM on the matrix cores (k_brick_cg<XF, BF, FULL, UD>, the overload of the Kronecker-form
 // kernel in brick_kernels.hip that brick_cg2_launch takes when uniform_elem(c)), the uniformity check and
-// the element matrix of the PA setup (setup_uniform_elem).  The update kernel it feeds is in
+// the element matrix of the PA setup (setup_uniform_elem), and the class table of the Jacobi scale
+// (pa_uniform_diag: setup_uniform_diag, the UD flag of the apply).  The update kernel it feeds is in
 // brick_kernels.hip (k_cg_update_faces).
 #include <hip/hip_runtime.h>
 
@@ -88,8 +89,15 @@ constexpr bool um_group_padded() { return kUmRow[4 * G + 1] < 0 || kUmRow[4 * G 
 // apart (1, 7 or 61), so the two dofs of a 32-lane half already miss each other's banks and the reads
 // sit on the 2-way floor of the 16 element origins (2 ex + 18 ey doubles: 12 distinct bank pairs).
 // kinds 7 and 5 differ in A_e only.  FULL: every brick's patch lies inside the lattice.
+// UD (pa_uniform_diag): dinv is the 64-entry class table of the Jacobi scale, not the vector.  The wave
+// copies it to LDS (one load per lane, issued ahead of the gather) with a 1 behind it, and a position reads
+// that 1 if essential, else the entry of its class (udiag_class per axis).  A patch coordinate's class
+// comes from one scalar word per axis and brick, 2 bits per coordinate: the parity, 2 at coordinate 0 of
+// the first brick, 3 at the last lattice plane where the patch holds it.  The gather packs a position's
+// table offset into 9 bits, three positions per register.  Positions past the lattice read some finite
+// entry and keep d = 0 (r and d_old load 0 there).
 // ================================================================================================
-template <bool XF, bool BF, bool FULL>
+template <bool XF, bool BF, bool FULL, bool UD>
 __global__ void __launch_bounds__(64, 2)
 k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const double *__restrict__ d_old,
            double *__restrict__ d_new, double *__restrict__ face, const double *__restrict__ amat,
@@ -101,6 +109,7 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
     static_assert(S == 9, "um_slot_off is written for the 9^3 patch");
     __shared__ double s_in[S3];
     __shared__ double s_out[S3];
+    __shared__ double s_tab[UD ? kUdiagN + 1 : 1];  // the class table, then 1 (what an essential dof takes)
     if (st->done) return;
     brick_stagger(g);
     double beta = st->beta;
@@ -129,9 +138,21 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
     constexpr int NI = (S3 + 63) / 64;
     const int Lx = g.Lx, Lxy = g.Lx * g.Ly;
     const uint32_t nl = (uint32_t)Lxy * (uint32_t)g.Lz;
-    const auto br = brsrc(r, 8u * nl), bm = brsrc(dinv, 8u * nl), bo = brsrc(d_old, 8u * nl);
+    const auto br = brsrc(r, 8u * nl), bm = brsrc(dinv, UD ? 8u * kUdiagN : 8u * nl), bo = brsrc(d_old, 8u * nl);
     const auto be = brsrc(ess, nl), bd = brsrc(d_new, 8u * nl), bxf = brsrc(x, XF ? 8u * nl : 0u);
-    double rv[NI], mv[NI], ov[NI], xv[NI];
+    double rv[NI], mv[UD ? 1 : NI], ov[NI], xv[NI];
+    uint32_t cw[UD ? (NI + 2) / 3 : 1] = {};  // UD: the positions' table byte offsets, 9 bits each
+    uint32_t wx = 0, wy = 0, wz = 0;          // UD: the axes' class words
+    if constexpr (UD) {
+        // (e: the patch coordinate of the axis' last lattice plane, past the patch in all but the last brick)
+        auto axis_word = [](int b0, int e) {
+            return 0x4444u | (b0 == 0 ? 2u : 0u) | (e < S ? 3u << (2 * e) : 0u);
+        };
+        wx = axis_word(bx, g.Lx - 1 - gx0);
+        wy = axis_word(by, g.Ly - 1 - gy0);
+        wz = axis_word(bz, g.Lz - 1 - gz0);
+        mv[0] = bload(bm, 8u * (uint32_t)t);
+    }
     uint32_t woffv[NI];
     uint32_t dbits = 0, ebits = 0;
     uint8_t ev[NI];
@@ -150,7 +171,15 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
         const bool in = i < S3 && (FULL || (gx0 + px < g.Lx && gy0 + py < g.Ly && gz < g.Lz));
         const uint32_t off = in ? 8u * gid : kOOB;
         rv[k] = bload(br, off);
-        mv[k] = bload(bm, off);
+        if constexpr (UD) {
+            const uint32_t cl = ((wx >> (2 * px)) & 3u) | (((wy >> (2 * py)) & 3u) << 2) | (((wz >> (2 * pz)) & 3u) << 4);
+            cw[k / 3] |= cl << (9 * (k % 3) + 3);
+            // (packed here, between this step's loads and the next's: left to the scheduler, the twelve
+            // steps' coordinates stay live until the form, 36 registers and a wave per SIMD)
+            asm volatile("" : "+v"(cw[k / 3]));
+        } else {
+            mv[k] = bload(bm, off);
+        }
         ov[k] = bload(bo, off);
         ev[k] = __builtin_amdgcn_raw_buffer_load_b8(be, in ? gid : kOOB, 0, 0);
         const bool writer = in && (px < S - 1 || lastx) && (py < S - 1 || lasty) && (pz < S - 1 || lastz);
@@ -162,8 +191,17 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
         constexpr int k = decltype(kc)::value;
         const unsigned i = t + 64 * k;
         if (k == NI - 1 && i >= S3) return;
-        const double dn = mv[k] * rv[k] + beta * ov[k];  // 0 outside the lattice
         const bool e = ev[k] != 0;
+        double m;
+        if constexpr (UD) {
+            // (an essential position reads the 1 behind the table: one 32-bit select on the offset instead
+            // of a 64-bit select on the value)
+            const uint32_t o = e ? 8u * kUdiagN : (cw[k / 3] >> (9 * (k % 3))) & (8u * (kUdiagN - 1));
+            m = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(s_tab) + o);
+        } else {
+            m = mv[k];
+        }
+        const double dn = m * rv[k] + beta * ov[k];  // 0 outside the lattice
         bstore(bd, woffv[k], dn);
         if constexpr (XF) bstore(bxf, woffv[k], xv[k] + alpha_prev * ov[k]);
         den += (e && ((dbits >> k) & 1u)) ? dn * dn : 0.0;  // (A_c d)_i = d_i on ess dofs
@@ -191,6 +229,11 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
             if (stop) return;
             beta = B / st->nom;
         }
+    }
+    if constexpr (UD) {
+        s_tab[t] = mv[0];
+        if (t == 0) s_tab[kUdiagN] = 1.0;
+        __syncthreads();
     }
     static_for<0, NI>(form);
     __syncthreads();
@@ -311,21 +354,29 @@ hipError_t launch_brick_um(cdfem_ctx *c, const BrickGeom &g, unsigned nbrick_lau
     const double *upart = c->d_part + c->nblk;                  // the den-fold update's partials
     double *const dpart = c->den_out ? c->den_out : c->d_part;  // the apply's den partials
     const bool full = c->sx % kBrick == 0 && c->sy % kBrick == 0 && c->sz % kBrick == 0;
-#define CDFEM_BUM(XF_, BF_, FU_)                                                                              \
+    // the Jacobi scale from the class table (not under pc = none, whose dinv is the ones vector)
+    const bool ud = uniform_diag(c) && dinv == c->d_dinv;
+    if (ud) dinv = c->d_udiag;
+#define CDFEM_BUM(XF_, BF_, FU_, UD_)                                                                              \
     do {                                                                                                      \
         if (whole)                                                                                            \
-            CDFEM_LAUNCH(c, (k_brick_cg<XF_, BF_, FU_>), grid, block, 0, r, dinv, d_old, d_new, c->d_face,      \
+            CDFEM_LAUNCH(c, (k_brick_cg<XF_, BF_, FU_, UD_>), grid, block, 0, r, dinv, d_old, d_new, c->d_face,      \
                          c->d_uelem, c->d_ess, g, c->zlo_shared, dpart, c->d_state, x, upart, nupart, kk,       \
                          c->d_gsum, c->d_gcnt, c->den_grp, c->nblk);                                            \
         else                                                                                                  \
-            hipLaunchKernelGGL((k_brick_cg<XF_, BF_, FU_>), grid, block, 0, s, r, dinv, d_old, d_new, c->d_face, \
+            hipLaunchKernelGGL((k_brick_cg<XF_, BF_, FU_, UD_>), grid, block, 0, s, r, dinv, d_old, d_new, c->d_face, \
                                c->d_uelem, c->d_ess, g, c->zlo_shared, dpart, c->d_state, x, upart, nupart, kk, \
                                c->d_gsum, c->d_gcnt, c->den_grp, c->nblk);                                      \
     } while (0)
+#define CDFEM_BUM3(XF_, BF_, FU_)                                                                             \
+    do {                                                                                                      \
+        if (ud) CDFEM_BUM(XF_, BF_, FU_, true);                                                               \
+        else CDFEM_BUM(XF_, BF_, FU_, false);                                                                 \
+    } while (0)
 #define CDFEM_BUM2(XF_, BF_)                                                                                  \
     do {                                                                                                      \
-        if (full) CDFEM_BUM(XF_, BF_, true);                                                                  \
-        else CDFEM_BUM(XF_, BF_, false);                                                                      \
+        if (full) CDFEM_BUM3(XF_, BF_, true);                                                                 \
+        else CDFEM_BUM3(XF_, BF_, false);                                                                     \
     } while (0)
     if (kk >= 0) {
         if (x) CDFEM_BUM2(true, true);
@@ -335,6 +386,7 @@ hipError_t launch_brick_um(cdfem_ctx *c, const BrickGeom &g, unsigned nbrick_lau
         else CDFEM_BUM2(false, false);
     }
 #undef CDFEM_BUM2
+#undef CDFEM_BUM3
 #undef CDFEM_BUM
     return hipGetLastError();
 }
@@ -435,6 +487,99 @@ hipError_t setup_uniform_elem(cdfem_ctx *c)
         return e;
     }
     c->d_uelem = static_cast<double *>(d);
+    return hipSuccess;
+}
+
+// ---- pa_uniform_diag: the Jacobi scale of a uniform box as 64 class values ------------------------
+__device__ __forceinline__ int udiag_index(int gid, int Lx, int Ly, int Lz)
+{
+    const int gx = gid % Lx, gy = (gid / Lx) % Ly, gz = gid / (Lx * Ly);
+    return udiag_class(gx, Lx) + 4 * udiag_class(gy, Ly) + 16 * udiag_class(gz, Lz);
+}
+
+// first[class] = the lowest lattice index among the class's non-essential dofs (first = ~0 on entry): a
+// minimum per workgroup in LDS, then one global atomic minimum per class the workgroup met
+__global__ void __launch_bounds__(256)
+k_udiag_first(const uint8_t *__restrict__ ess, int Lx, int Ly, int Lz, uint32_t *__restrict__ first)
+{
+    __shared__ uint32_t lo[kUdiagN];
+    if (threadIdx.x < kUdiagN) lo[threadIdx.x] = ~0u;
+    __syncthreads();
+    const int n = Lx * Ly * Lz;
+    for (int gid = blockIdx.x * blockDim.x + threadIdx.x; gid < n; gid += gridDim.x * blockDim.x)
+        if (!ess[gid]) atomicMin(&lo[udiag_index(gid, Lx, Ly, Lz)], (uint32_t)gid);
+    __syncthreads();
+    if (threadIdx.x < kUdiagN && lo[threadIdx.x] != ~0u) atomicMin(&first[threadIdx.x], lo[threadIdx.x]);
+}
+
+// the table (1 for a class without a non-essential dof: any finite value serves), one workgroup of 64
+__global__ void __launch_bounds__(kUdiagN)
+k_udiag_fill(const double *__restrict__ dinv, const uint32_t *__restrict__ first, double *__restrict__ tab)
+{
+    const uint32_t f = first[threadIdx.x];
+    tab[threadIdx.x] = f != ~0u ? dinv[f] : 1.0;
+}
+
+// flags[0]: an entry of dinv is not what the kernels would take in its place (1 on an essential dof, else
+// within tol, relative, of the class entry); flags[1]: some non-essential entry differs from its class
+// entry at all (plain vector stores of the same value)
+__global__ void __launch_bounds__(256)
+k_udiag_check(const double *__restrict__ dinv, const uint8_t *__restrict__ ess, const double *__restrict__ tab,
+              int Lx, int Ly, int Lz, double tol, int *__restrict__ flags)
+{
+    const int n = Lx * Ly * Lz;
+    bool bad = false, inexact = false;
+    for (int gid = blockIdx.x * blockDim.x + threadIdx.x; gid < n; gid += gridDim.x * blockDim.x) {
+        const double m = dinv[gid];
+        if (ess[gid]) {
+            bad |= m != 1.0;
+        } else {
+            const double tv = tab[udiag_index(gid, Lx, Ly, Lz)];
+            bad |= !(fabs(m - tv) <= tol * fabs(tv));
+            inexact |= m != tv;
+        }
+    }
+    if (bad) flags[0] = 1;
+    if (inexact) flags[1] = 1;
+}
+
+hipError_t setup_uniform_diag(cdfem_ctx *c)
+{
+    hipError_t e = hipSuccess;
+    if (c->d_udiag) {
+        e = hipFree(c->d_udiag);
+        c->d_udiag = nullptr;
+        if (e != hipSuccess) return e;
+    }
+    c->udiag_bitwise = false;
+    if (c->d_uelem == nullptr || !c->structured || c->dim != 3 || c->p != 2 || c->perm_space ||
+        c->nl != c->Lx * c->Ly * c->Lz || c->nl >= ((int64_t)1 << 31))
+        return hipSuccess;
+    // one allocation: the table, the classes' first indices, the two flags
+    void *buf = nullptr;
+    if ((e = hipMalloc(&buf, sizeof(double) * kUdiagN + sizeof(uint32_t) * (kUdiagN + 2))) != hipSuccess) return e;
+    double *tab = static_cast<double *>(buf);
+    uint32_t *first = reinterpret_cast<uint32_t *>(tab + kUdiagN);
+    int *flags = reinterpret_cast<int *>(first + kUdiagN);
+    int hflags[2] = {1, 1};
+    const int Lx = (int)c->Lx, Ly = (int)c->Ly, Lz = (int)c->Lz;
+    const dim3 grid((unsigned)std::min<int64_t>((c->nl + 255) / 256, 1024)), block(256);
+    e = hipMemsetAsync(first, 0xff, sizeof(uint32_t) * kUdiagN, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, 2 * sizeof(int), c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_udiag_first, grid, block, 0, c->stream, c->d_ess, Lx, Ly, Lz, first);
+        hipLaunchKernelGGL(k_udiag_fill, dim3(1), dim3(kUdiagN), 0, c->stream, c->d_dinv, first, tab);
+        hipLaunchKernelGGL(k_udiag_check, grid, block, 0, c->stream, c->d_dinv, c->d_ess, tab, Lx, Ly, Lz, 1e-14, flags);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(hflags, flags, sizeof(hflags), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || hflags[0]) {  // not class-constant: the solve streams the vector
+        const hipError_t ef = hipFree(buf);
+        return e != hipSuccess ? e : ef;
+    }
+    c->d_udiag = tab;
+    c->udiag_bitwise = hflags[1] == 0;
     return hipSuccess;
 }
 

@@ -138,6 +138,7 @@ void free_mesh(cdfem_ctx *c)
     dfree(c->d_sptr); dfree(c->d_srows); dfree(c->d_scols); dfree(c->d_smap); dfree(c->d_sdel); dfree(c->d_svals);
     dfree(c->d_swide);
     dfree(c->d_uelem);
+    dfree(c->d_udiag);
     dfree(c->d_hoelem);
     c->d_sdel = nullptr;
     c->d_swide = nullptr;
@@ -414,6 +415,20 @@ void ensure_dinv(cdfem_ctx *c)
     }
     interface_sum(c, diag);  // shared planes: the full diagonal (both ranks' elements)
     HIPCHK(launch_dinv(c, diag, c->d_dinv));
+    // pa_uniform_diag: the class table of a uniform p = 2 box, checked against the vector on the device.
+    // Several ranks keep it only if every rank's check passed (each picks a class's entry at the same
+    // (x, y) of a shared plane, so the ranks' copies of the plane stay bitwise equal).
+    HIPCHK(setup_uniform_diag(c));
+    if (multi_rank(c)) {
+        const double mine = c->d_udiag ? 1.0 : 0.0;
+        double all = mine;
+        if (!c->d_small) c->d_small = dalloc<double>(8);
+        HIPCHK(hipMemcpyAsync(c->d_small, &mine, sizeof(double), hipMemcpyHostToDevice, c->stream));
+        comm_allreduce(c, c->d_small, 1);
+        HIPCHK(hipMemcpyAsync(&all, c->d_small, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (all != (double)c->nranks) dfree(c->d_udiag);
+    }
     c->dinv_ready = true;
 }
 
@@ -1920,6 +1935,9 @@ int cdfem_set_option(cdfem_ctx *c, const char *key, int value)
         } else if (k == "pa_uniform") {  // the matrix is formed by cdfem_pa_setup; 0 leaves it unused
             if (value != 0 && value != 1) throw ArgError("pa_uniform must be 0 or 1");
             c->pa_uniform = value;
+        } else if (k == "pa_uniform_diag") {  // the table is built with the Jacobi scale; 0 leaves it unused
+            if (value != 0 && value != 1) throw ArgError("pa_uniform_diag must be 0 or 1");
+            c->pa_uniform_diag = value;
         } else if (k == "ho_uniform") {  // the matrix is formed by cdfem_pa_setup when 1; 0 leaves it unused
             if (value != 0 && value != 1) throw ArgError("ho_uniform must be 0 or 1");
             c->ho_uniform = value;
@@ -2217,10 +2235,12 @@ int cdfem_kernel_bytes(cdfem_ctx *c, int k, double *bytes)
                                   // (+ x read and written by its writer brick under the x-fold)
                 // (pa_uniform: one element matrix, 14 x 64 operand doubles, instead of the factor stream)
                 // (pa_geom: the element's mask and 21 map coefficients instead of its stream)
+                // (pa_uniform_diag: the 64-entry class table instead of the gathered M^-1)
                 *bytes = (uniform_elem(c) ? 8.0 * 14 * 64
                           : pa_geom_on(c) ? 8.0 * GeomLayout::kNC * ne
-                                          : 8.0 * c->ncomp * (c->d_qaff ? 1.0 : nq) * ne) + 24.0 * nl +
-                         1.0 * nl + 8.0 * nl + patches + (xf ? 16.0 * nl : 0.0);
+                                          : 8.0 * c->ncomp * (c->d_qaff ? 1.0 : nq) * ne) +
+                         (uniform_diag(c) ? 16.0 * nl + 8.0 * kUdiagN : 24.0 * nl) + 1.0 * nl + 8.0 * nl + patches +
+                         (xf ? 16.0 * nl : 0.0);
                 return CDFEM_OK;
             case CDFEM_K_E2L:     // the Mult's row sums: the patch buffer + ess flags + y (brick_mult_pb,
                                   // Kronecker form), or face partials + x, ess, y of the face dofs
@@ -2229,7 +2249,8 @@ int cdfem_kernel_bytes(cdfem_ctx *c, int k, double *bytes)
                 return CDFEM_OK;
             case CDFEM_K_UPDATE:  // x, d, r, M^-1 read, ess, x, r write + the patch outputs (each once);
                                   // x-fold: r, M^-1, ess and r write only
-                *bytes = (xf ? 25.0 : 49.0) * nl + patches;
+                // (pa_uniform_diag: no M^-1 stream; the essential flag it reads instead is counted above)
+                *bytes = (xf ? 25.0 : 49.0) * nl + patches - (uniform_diag(c) ? 8.0 * nl : 0.0);
                 return CDFEM_OK;
             default: throw ArgError("kernel not launched on the brick path");
             }

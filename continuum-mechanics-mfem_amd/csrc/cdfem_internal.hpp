@@ -178,6 +178,11 @@ struct cdfem_ctx {
                                         // gives), the p = 2 brick CG applies that element's 27 x 27 matrix on
                                         // the matrix cores (brick_um.hip k_brick_cg<XF, BF, FULL>); 0 keeps the Kronecker form
     double *d_uelem = nullptr;          // pa_uniform: the common element matrix in MFMA A-operand order
+    int pa_uniform_diag = 1;            // set_option "pa_uniform_diag": with pa_uniform, the Jacobi-CG apply and update take
+                                        // M^-1 from the 64 lattice-class values of d_udiag instead of streaming d_dinv
+    double *d_udiag = nullptr;          // [kUdiagN] the class table (setup_uniform_diag, valid while dinv_ready;
+                                        // null when the device check found d_dinv not class-constant)
+    bool udiag_bitwise = false;         //   every non-essential entry of d_dinv equals its class entry bitwise
     int ho_uniform = 0;                 // set_option "ho_uniform": the p = 3, 4 block CG (2 x 2 x 4 blocks) applies the
                                         // common N x N element matrix of a uniform box (N = 64, 125) as one GEMM on
                                         // the matrix cores (k_hobrick_um); read by cdfem_pa_setup, 0 afterwards
@@ -387,6 +392,13 @@ inline int pa_form(const cdfem_ctx *c) { return pa_geom_on(c) ? 3 : pa_af(c); }
 // the brick CG applies the common element matrix of a uniform box (pa_uniform: formed at the PA setup;
 // set_option "pa_uniform" 0 switches back to the Kronecker form without a new setup)
 inline bool uniform_elem(const cdfem_ctx *c) { return c->d_uelem != nullptr && c->pa_uniform != 0 && pa_af(c) == 2; }
+// the uniform-box brick CG under Jacobi takes M^-1 from the class table (pa_uniform_diag: built and checked
+// against d_dinv by ensure_dinv; set_option "pa_uniform_diag" 0 streams the vector again)
+constexpr int kUdiagN = 64;
+inline bool uniform_diag(const cdfem_ctx *c)
+{
+    return c->d_udiag != nullptr && c->dinv_ready && c->pa_uniform_diag != 0 && uniform_elem(c);
+}
 
 // ---- kernel launchers (pa_kernels.hip) -------------------------------------------------------
 hipError_t launch_setup_qdata(cdfem_ctx *c, const double *d_kappa_q, const double *d_kmat_q, double kappa, double alpha,
@@ -458,6 +470,11 @@ hipError_t launch_update_fin(cdfem_ctx *c, int nparts, int64_t off = 0);
 // that every element's factors equal the first element's (within 1e-14 of the largest) and, if so, forms
 // that element's 27 x 27 matrix (column j = the Kronecker core on e_j) in d_uelem (freed otherwise)
 hipError_t setup_uniform_elem(cdfem_ctx *c);
+// pa_uniform_diag: after launch_dinv on such a box (d_uelem present, one dof order), d_udiag[cx + 4 cy + 16 cz] =
+// d_dinv at the lowest lattice index among the non-essential dofs of class (cx, cy, cz) (udiag_class per
+// axis, brick_core.hpp); kept only if the device check finds every non-essential entry of d_dinv within
+// 1e-14 (relative) of its class entry and every essential entry equal to 1 (freed otherwise)
+hipError_t setup_uniform_diag(cdfem_ctx *c);
 // ho_uniform: the same for a structured p = 3, 4 box whose CG runs on 2 x 2 x 4 blocks (kinds 7 or 5, one
 // rank): every element's factors against element 0's, each component within 1e-14 of its own magnitude;
 // if so the 64 x 64 / 125 x 125 element matrix goes to d_hoelem (freed otherwise)

@@ -274,6 +274,15 @@ int cdfem_fp64_bench(cdfem_ctx *ctx, int mode, int reps, double *tflops);
  *              CG apply then runs it as a GEMM on the matrix cores (56 v_mfma_f64_16x16x4_f64 per 64
  *              elements; the same operator to rounding).  0 = the Kronecker form (takes effect without a
  *              new setup; 1 needs one).  The GMRES Mult and the other applies keep the Kronecker form.
+ * "pa_uniform_diag": 1 (default) — where pa_uniform's matrix is in use, the Jacobi scale of such a box takes 64
+ *              values (per axis a lattice coordinate is element-interior, shared by two elements, on the
+ *              first plane or on the last; essential dofs take 1).  When the scale is formed, the library
+ *              fills that table from it (a class's entry = the vector's at the class's lowest non-essential
+ *              lattice index) and checks the vector against it on the device (1e-14 relative, essential
+ *              entries exactly 1; several ranks: on every rank).  If the check passes, the Jacobi-CG apply
+ *              and update of the brick path read the table from LDS instead of streaming the vector (17 MB
+ *              less per kernel and iteration at 64^3; the iterates agree to rounding).  0 =
+ *              stream the vector; read at solve time.  pc = none, GMRES and every other path keep the vector.
  * "ho_uniform": 0 (default) or 1 — the same for the high-order block CG, read by cdfem_pa_setup.  With 1
  *              the setup checks whether every element's factors equal element 0's, each component within
  *              1e-14 of its own magnitude, and, if so, forms that element's N x N matrix once (N = 64 at
