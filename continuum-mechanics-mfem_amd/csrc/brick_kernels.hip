@@ -23,6 +23,7 @@
 #include <cmath>
 
 #include "cdfem_internal.hpp"
+#include "dispatch.hpp"
 #include "brick_core.hpp"
 #include "pa_core.hpp"
 #include "reduce.hpp"
@@ -387,18 +388,19 @@ static hipError_t brick_launch(cdfem_ctx *c, const double *x, const double *dinv
     const bool mpb = brick_mult_pb_on(c);
     if (which & 1) {
         const Tab<D1, Q1> T = make_tab<D1, Q1>(c->rule_op);
-#define CDFEM_B3(AF_, QD_)                                                                                    \
-    hipLaunchKernelGGL((k_brick3d<D1, Q1, K, MODE, AF_>), dim3(c->nblk), dim3(64), 0, c->stream, x, y, c->d_face, \
-                       QD_, c->d_ess, T, g)
-        if (pa_af(c) == 2 && mpb)
-            hipLaunchKernelGGL((k_brick3d<D1, Q1, K, MODE, 2, true>), dim3(c->nblk), dim3(64), 0, c->stream, x, y,
-                               c->d_face, c->d_qaff, c->d_ess, T, g);
-        else if (pa_af(c) == 2) CDFEM_B3(2, c->d_qaff);
-        else if (pa_af(c) == 1) CDFEM_B3(1, c->d_qaff);
-        else if (pa_geom_on(c)) CDFEM_B3(3, c->d_geom);
-        else CDFEM_B3(0, c->d_qd);
-#undef CDFEM_B3
-        const hipError_t e = hipGetLastError();
+        const int af = pa_form(c);
+        const double *qd = af == 3 ? c->d_geom : af ? c->d_qaff : c->d_qd;
+        const hipError_t e = dispatch_value<0, 1, 2, 3>(af, hipErrorInvalidValue, [&](auto AF) {
+            // (PBO, the patch for k_brick_patch_sum: the Kronecker form only)
+            return dispatch_bools(mpb && AF() == 2, [&](auto PBO) {
+                if constexpr (PBO() && AF() != 2) return hipErrorInvalidValue;
+                else {
+                    hipLaunchKernelGGL((k_brick3d<D1, Q1, K, MODE, AF(), PBO()>), dim3(c->nblk), dim3(64), 0, c->stream,
+                                       x, y, c->d_face, qd, c->d_ess, T, g);
+                    return hipGetLastError();
+                }
+            });
+        });
         if (e != hipSuccess) return e;
     }
     if ((which & 2) && mpb) {
@@ -414,35 +416,20 @@ static hipError_t brick_launch(cdfem_ctx *c, const double *x, const double *dinv
                            c->d_face, c->d_ess, g, c->d_part + c->nblk, c->d_state);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-
     }
     return hipGetLastError();
-}
-
-template <int D1, int Q1, int MODE>
-static hipError_t brick_kinds(cdfem_ctx *c, const double *x, const double *dinv, double *d, double *y,
-                              int which)
-{
-    switch (c->kinds) {
-    case 1: return brick_launch<D1, Q1, 1, MODE>(c, x, dinv, d, y, which);
-    case 2: return brick_launch<D1, Q1, 2, MODE>(c, x, dinv, d, y, which);
-    case 3: return brick_launch<D1, Q1, 3, MODE>(c, x, dinv, d, y, which);
-    case 4: return brick_launch<D1, Q1, 4, MODE>(c, x, dinv, d, y, which);
-    case 5: return brick_launch<D1, Q1, 5, MODE>(c, x, dinv, d, y, which);
-    case 6: return brick_launch<D1, Q1, 6, MODE>(c, x, dinv, d, y, which);
-    case 7: return brick_launch<D1, Q1, 7, MODE>(c, x, dinv, d, y, which);
-    default: return hipErrorInvalidValue;
-    }
 }
 
 template <int MODE>
 static hipError_t brick_dispatch(cdfem_ctx *c, const double *x, const double *dinv, double *d, double *y,
                                  int which)
 {
-    const int q1 = c->rule_op.q1;
-    if (c->p == 1 && q1 == 3) return brick_kinds<2, 3, MODE>(c, x, dinv, d, y, which);
-    if (c->p == 2 && q1 == 4) return brick_kinds<3, 4, MODE>(c, x, dinv, d, y, which);
-    return hipErrorInvalidValue;
+    if (c->rule_op.q1 != c->p + 2) return hipErrorInvalidValue;
+    return dispatch_value<1, 2>(c->p, hipErrorInvalidValue, [&](auto P) {
+        return dispatch_kinds(c->kinds, hipErrorInvalidValue, [&](auto K) {
+            return brick_launch<P() + 1, P() + 2, K(), MODE>(c, x, dinv, d, y, which);
+        });
+    });
 }
 
 hipError_t launch_brick_mult(cdfem_ctx *c, const double *x, double *y, bool constrained, int which)
@@ -450,10 +437,6 @@ hipError_t launch_brick_mult(cdfem_ctx *c, const double *x, double *y, bool cons
     return constrained ? brick_dispatch<1>(c, x, nullptr, nullptr, y, which)
                        : brick_dispatch<0>(c, x, nullptr, nullptr, y, which);
 }
-
-
-
-
 
 // ================================================================================================
 // Brick CG, version 2 (the Krylov hot loop on structured boxes): 2 streaming kernels + 2 one-block
@@ -1197,15 +1180,6 @@ static hipError_t brick_cg2_launch(cdfem_ctx *c, const double *r, const double *
     const double *upart = c->d_part + c->nblk;  // the den-fold update's partials
     double *const dpart = c->den_out ? c->den_out : c->d_part;  // the apply's den partials
     const int grp = c->den_grp, nbrick = c->nblk;               // (grouped: sums into d_gsum)
-#define CDFEM_BCG6(AFF_, W_, XF_, BF_, FU_, MX_)                                                            \
-    if (whole)                                                                                               \
-        CDFEM_LAUNCH(c, (k_brick_cg<D1, Q1, K, AFF_, W_, XF_, BF_, FU_, MX_>), grid, block, 0, r, dinv, d_old, d_new, q, \
-                     c->d_face, qd, c->d_ess, T, g, c->zlo_shared, dpart, c->d_state, x, upart, run.nupart,     \
-                     run.kk, c->d_gsum, c->d_gcnt, grp, nbrick);                                             \
-    else                                                                                                     \
-        hipLaunchKernelGGL((k_brick_cg<D1, Q1, K, AFF_, W_, XF_, BF_, FU_, MX_>), grid, block, 0, run.s, r, dinv, \
-                           d_old, d_new, q, c->d_face, qd, c->d_ess, T, g, c->zlo_shared, dpart, c->d_state, x, \
-                           upart, run.nupart, run.kk, c->d_gsum, c->d_gcnt, grp, nbrick)
     // pa_uniform: the common element matrix on the matrix cores (brick_um.hip), p = 2, the full operator and
     // the symmetric kK + sM of the bench (kinds 7, 5: the matrix setup_uniform_elem forms); other kinds keep
     // the Kronecker form
@@ -1216,38 +1190,23 @@ static hipError_t brick_cg2_launch(cdfem_ctx *c, const double *r, const double *
     // (brick_mfma: the MFMA x stage, built for the Kronecker form of the full operator at p = 2)
     constexpr bool kMX = K == 7 && D1 == 3;
     const bool mx = kMX && c->brick_mfma != 0;
-#define CDFEM_BCG5(AFF_, W_, XF_, BF_, FU_)                                                                 \
-    if constexpr (kMX && AFF_ == 2) {                                                                        \
-        if (mx) { CDFEM_BCG6(AFF_, W_, XF_, BF_, FU_, 1); }                                                  \
-        else { CDFEM_BCG6(AFF_, W_, XF_, BF_, FU_, 0); }                                                     \
-    } else {                                                                                                 \
-        CDFEM_BCG6(AFF_, W_, XF_, BF_, FU_, 0);                                                              \
-    }
-#define CDFEM_BCG4(AFF_, W_, XF_, BF_)                                                                      \
-    if (full) { CDFEM_BCG5(AFF_, W_, XF_, BF_, true); } else { CDFEM_BCG5(AFF_, W_, XF_, BF_, false); }
-#define CDFEM_BCG3(AFF_, W_, XF_) CDFEM_BCG5(AFF_, W_, XF_, false, false)
-#define CDFEM_BCG(AFF_, W_) CDFEM_BCG3(AFF_, W_, false)
     // every brick's patch inside the lattice (element counts multiples of 4): no per-position bounds
     const bool full = c->sx % kBrick == 0 && c->sy % kBrick == 0 && c->sz % kBrick == 0;
-    if (pa_af(c) == 2 && run.kk >= 0) {
-        if (x) { CDFEM_BCG4(2, 2, true, true); }
-        else { CDFEM_BCG4(2, 2, false, true); }
-    } else if (pa_af(c) == 2) {
-        if (x) { CDFEM_BCG4(2, 2, true, false); }
-        else { CDFEM_BCG4(2, 2, false, false); }
-    } else if (pa_af(c) == 1) {
-        CDFEM_BCG(1, 1);
-    } else if (pa_geom_on(c)) {
-        CDFEM_BCG(3, 1);
-    } else {
-        CDFEM_BCG(0, 1);
-    }
-#undef CDFEM_BCG
-#undef CDFEM_BCG3
-#undef CDFEM_BCG4
-#undef CDFEM_BCG5
-#undef CDFEM_BCG6
-    return hipGetLastError();
+    return dispatch_value<0, 1, 2, 3>(pa_form(c), hipErrorInvalidValue, [&](auto AF) {
+        // the x fold, the betanom fold, the full lattice and the MFMA x stage: the Kronecker form only
+        constexpr bool kKron = AF() == 2;
+        return dispatch_bools(kKron && x != nullptr, kKron && run.kk >= 0, kKron && full, kKron && mx,
+                              [&](auto XF, auto BF, auto FU, auto MX) {
+            if constexpr ((!kKron && (XF() || BF() || FU() || MX())) || (MX() && !kMX)) return hipErrorInvalidValue;
+            else {
+                const auto kern = k_brick_cg<D1, Q1, K, AF(), kKron ? 2 : 1, XF(), BF(), FU(), MX() ? 1 : 0>;
+                CDFEM_LAUNCH_ON(c, whole, run.s, kern, grid, block, 0, r, dinv, d_old, d_new, q, c->d_face, qd,
+                                c->d_ess, T, g, c->zlo_shared, dpart, c->d_state, x, upart, run.nupart, run.kk,
+                                c->d_gsum, c->d_gcnt, grp, nbrick);
+                return hipGetLastError();
+            }
+        });
+    });
 }
 
 template <int D1, int Q1, unsigned K, int EZ = kHoBrick>
@@ -1269,57 +1228,36 @@ static hipError_t hobrick_launch(cdfem_ctx *c, const double *r, const double *di
         if (ho_uniform_elem(c)) return launch_hobrick_um(c, g, r, dinv, d_old, d_new, x);  // (hobrick_um.hip)
     }
     const dim3 grid((unsigned)c->hb_nblk), block(NT);
-#define CDFEM_HB(XF_, MF_)                                                                                     \
-    CDFEM_LAUNCH(c, (k_hobrick_cg<D1, Q1, K, XF_, MF_, EZ>), grid, block, 0, r, dinv, d_old, d_new, c->d_face, c->d_qaff, \
-                 c->d_ess, T, g, c->sx, c->sy, c->sz, c->d_hbpart, c->d_state, x, kt, c->zlo_shared)
-    if constexpr (K == 7 && EZ == kHoBrick) {  // the MFMA x stage: the full operator on 2^3 blocks (ho_brick_mfma)
-        if (c->ho_brick_mfma) {
-            if (x) { CDFEM_HB(true, true); } else { CDFEM_HB(false, true); }
+    // the MFMA x stage: the full operator on 2^3 blocks (ho_brick_mfma)
+    constexpr bool kMF = K == 7 && EZ == kHoBrick;
+    return dispatch_bools(x != nullptr, kMF && c->ho_brick_mfma != 0, [&](auto XF, auto MF) {
+        if constexpr (MF() && !kMF) return hipErrorInvalidValue;
+        else {
+            const auto kern = k_hobrick_cg<D1, Q1, K, XF(), MF(), EZ>;
+            CDFEM_LAUNCH(c, kern, grid, block, 0, r, dinv, d_old, d_new, c->d_face, c->d_qaff, c->d_ess, T, g, c->sx,
+                         c->sy, c->sz, c->d_hbpart, c->d_state, x, kt, c->zlo_shared);
             return hipGetLastError();
         }
-    }
-    if (x) { CDFEM_HB(true, false); } else { CDFEM_HB(false, false); }
-#undef CDFEM_HB
-    return hipGetLastError();
+    });
 }
 
 static hipError_t brick_cg2_run(cdfem_ctx *c, const double *r, const double *dinv, const double *d_old,
                                 double *d_new, double *q, const BrickRun &run, double *x)
 {
-    const int q1 = c->rule_op.q1;
+    if (c->rule_op.q1 != c->p + 2) return hipErrorInvalidValue;
     if (c->p >= 3) {  // 2^3-element blocks, one launch (one rank)
         if (run.nlay != c->hb_nbz || run.kk >= 0) return hipErrorInvalidValue;
-#define CDFEM_HK(D1_, Q1_)                                                                          \
-    switch (c->kinds) {                                                                             \
-    case 1: return hobrick_launch<D1_, Q1_, 1>(c, r, dinv, d_old, d_new, x);                        \
-    case 2: return hobrick_launch<D1_, Q1_, 2>(c, r, dinv, d_old, d_new, x);                        \
-    case 3: return hobrick_launch<D1_, Q1_, 3>(c, r, dinv, d_old, d_new, x);                        \
-    case 4: return hobrick_launch<D1_, Q1_, 4>(c, r, dinv, d_old, d_new, x);                        \
-    case 5: return hobrick_launch<D1_, Q1_, 5>(c, r, dinv, d_old, d_new, x);                        \
-    case 6: return hobrick_launch<D1_, Q1_, 6>(c, r, dinv, d_old, d_new, x);                        \
-    case 7: return hobrick_launch<D1_, Q1_, 7>(c, r, dinv, d_old, d_new, x);                        \
-    default: return hipErrorInvalidValue;                                                           \
+        return dispatch_value<3, 4>(c->p, hipErrorInvalidValue, [&](auto P) {
+            return dispatch_kinds(c->kinds, hipErrorInvalidValue, [&](auto K) {
+                return hobrick_launch<P() + 1, P() + 2, K()>(c, r, dinv, d_old, d_new, x);
+            });
+        });
     }
-        if (c->p == 3 && q1 == 5) { CDFEM_HK(4, 5) }
-        if (c->p == 4 && q1 == 6) { CDFEM_HK(5, 6) }
-#undef CDFEM_HK
-        return hipErrorInvalidValue;
-    }
-#define CDFEM_K(D1_, Q1_)                                                                           \
-    switch (c->kinds) {                                                                             \
-    case 1: return brick_cg2_launch<D1_, Q1_, 1>(c, r, dinv, d_old, d_new, q, run, x);                 \
-    case 2: return brick_cg2_launch<D1_, Q1_, 2>(c, r, dinv, d_old, d_new, q, run, x);                 \
-    case 3: return brick_cg2_launch<D1_, Q1_, 3>(c, r, dinv, d_old, d_new, q, run, x);                 \
-    case 4: return brick_cg2_launch<D1_, Q1_, 4>(c, r, dinv, d_old, d_new, q, run, x);                 \
-    case 5: return brick_cg2_launch<D1_, Q1_, 5>(c, r, dinv, d_old, d_new, q, run, x);                 \
-    case 6: return brick_cg2_launch<D1_, Q1_, 6>(c, r, dinv, d_old, d_new, q, run, x);                 \
-    case 7: return brick_cg2_launch<D1_, Q1_, 7>(c, r, dinv, d_old, d_new, q, run, x);                 \
-    default: return hipErrorInvalidValue;                                                           \
-    }
-    if (c->p == 1 && q1 == 3) { CDFEM_K(2, 3) }
-    if (c->p == 2 && q1 == 4) { CDFEM_K(3, 4) }
-#undef CDFEM_K
-    return hipErrorInvalidValue;
+    return dispatch_value<1, 2>(c->p, hipErrorInvalidValue, [&](auto P) {
+        return dispatch_kinds(c->kinds, hipErrorInvalidValue, [&](auto K) {
+            return brick_cg2_launch<P() + 1, P() + 2, K()>(c, r, dinv, d_old, d_new, q, run, x);
+        });
+    });
 }
 
 hipError_t launch_brick_cg2(cdfem_ctx *c, const double *r, const double *dinv, const double *d_old,
@@ -1426,62 +1364,38 @@ hipError_t launch_cg_update_faces(cdfem_ctx *c, double *x, double *r, const doub
     // the apply's den partials the den fold sums: one per brick, or the group sums (den_grp > 1)
     const double *const apart = c->den_grp > 1 ? c->d_gsum : c->d_part;
     const int napart = c->den_grp > 1 ? den_parts(c) : c->nblk;
-#define CDFEM_UPD4(S_, XF_, PB_, DS_, EP_, UD_)                                                               \
-    hipLaunchKernelGGL((k_cg_update_faces<S_, XF_, PB_, DS_, EP_, SZ_, UD_>), dim3(ugrid), dim3(kRedThreads), 0, c->stream, x, \
-                       r, d, dinv, c->d_face, c->d_ess, g, fdx, fdxy, c->zlo_shared, remote_lo, remote_hi, upart, \
-                       c->d_state, (int)den_step, apart, napart)
     // predicated-load face sums: the patch buffer's byte offsets must fit 32 bits
     const bool pb = c->brick_upd_pb != 0 && brick_fits(c);
     // the apply's essential-row patch entries (k_brick_cg EP: the Kronecker form at p <= 2)
     const bool ep = pa_af(c) == 2 && c->p <= 2;
-    // pa_uniform_diag: the Jacobi scale from the class table (the p = 2 patch only: UD_ is false in every
-    // other instantiation; not under pc = none, whose dinv is the ones vector)
+    // pa_uniform_diag: the Jacobi scale from the class table (not under pc = none, whose dinv is the ones
+    // vector). Only the p = 2 patch (9 x 9 x 9) has the UD instantiation, so ud implies p == 2 here, and
+    // with it the swap of dinv for the table is right for the kernel that runs
     const bool ud = uniform_diag(c) && dinv == c->d_dinv && c->p == 2;
     if (ud) dinv = c->d_udiag;
-#define CDFEM_UPD3(S_, XF_, PB_, DS_)                                                                      \
-    if (ep && PB_) {                                                                                       \
-        if (ud) { CDFEM_UPD4(S_, XF_, PB_, DS_, PB_, (S_ == 9 && SZ_ == 9)); }                             \
-        else { CDFEM_UPD4(S_, XF_, PB_, DS_, PB_, false); }                                                \
-    } else if (ud) { CDFEM_UPD4(S_, XF_, PB_, DS_, false, (S_ == 9 && SZ_ == 9)); }                        \
-    else { CDFEM_UPD4(S_, XF_, PB_, DS_, false, false); }
-#define CDFEM_UPD2(S_, XF_, PB_)                                                                           \
-    if (ds) { CDFEM_UPD3(S_, XF_, PB_, true); } else { CDFEM_UPD3(S_, XF_, PB_, false); }
-#define CDFEM_UPD(S_)                                                                                       \
-    if (xfold) {                                                                                            \
-        if (pb) { CDFEM_UPD2(S_, true, true); } else { CDFEM_UPD2(S_, true, false); }                       \
-    } else {                                                                                                \
-        if (pb) { CDFEM_UPD2(S_, false, true); } else { CDFEM_UPD2(S_, false, false); }                     \
-    }
-    // (SZ_: the patch's z side, in scope of CDFEM_UPD4; p = 3, 4 with ho_block_z 4: 2 x 2 x 4 blocks)
-    if (c->p == 1) {
-        constexpr int SZ_ = kBrick * 1 + 1;
-        CDFEM_UPD(kBrick * 1 + 1);
-    } else if (c->p == 2 || (c->p == 4 && c->hb_ez == 2)) {  // (p = 4: 2^3-element blocks, the same 9^3 patch)
-        constexpr int SZ_ = kBrick * 2 + 1;
-        CDFEM_UPD(kBrick * 2 + 1);
-    } else if (c->p == 4 && c->hb_ez == 4) {
-        constexpr int SZ_ = 4 * 4 + 1;
-        CDFEM_UPD(kHoBrickEdge * 4 + 1);
-    } else if (c->p == 3 && c->hb_ez == 2) {
-        constexpr int SZ_ = kHoBrickEdge * 3 + 1;
-        CDFEM_UPD(kHoBrickEdge * 3 + 1);
-    } else if (c->p == 3 && c->hb_ez == 4) {
-        constexpr int SZ_ = 4 * 3 + 1;
-        CDFEM_UPD(kHoBrickEdge * 3 + 1);
-    } else {
-        return hipErrorInvalidValue;
-    }
-#undef CDFEM_UPD
-#undef CDFEM_UPD2
-#undef CDFEM_UPD3
-#undef CDFEM_UPD4
-    const hipError_t e = hipGetLastError();
+    // the patch: edge * p + 1 points a side, bricks of 4 elements at p <= 2, blocks of 2 x 2 x ho_block_z at
+    // p = 3, 4 (keyed 10 p + ho_block_z; p = 4 on 2^3 blocks shares the 9^3 patch with p = 2)
+    const int pez = c->p <= 2 ? c->p : 10 * c->p + c->hb_ez;
+    const hipError_t e = dispatch_value<1, 2, 32, 34, 42, 44>(pez, hipErrorInvalidValue, [&](auto PEZ) {
+        constexpr int P = PEZ() < 10 ? PEZ() : PEZ() / 10;
+        constexpr int S = (P <= 2 ? kBrick : kHoBrickEdge) * P + 1, SZ = (P <= 2 ? kBrick : PEZ() % 10) * P + 1;
+        return dispatch_bools(xfold, pb, ds, ep && pb, ud, [&](auto XF, auto PB, auto DS, auto EP, auto UD) {
+            // EP only together with PB; UD only for the 9 x 9 x 9 patch
+            if constexpr ((EP() && !PB()) || (UD() && !(S == 9 && SZ == 9))) return hipErrorInvalidValue;
+            else {
+                hipLaunchKernelGGL((k_cg_update_faces<S, XF(), PB(), DS(), EP(), SZ, UD()>), dim3(ugrid),
+                                   dim3(kRedThreads), 0, c->stream, x, r, d, dinv, c->d_face, c->d_ess, g, fdx, fdxy,
+                                   c->zlo_shared, remote_lo, remote_hi, upart, c->d_state, (int)den_step, apart,
+                                   napart);
+                return hipGetLastError();
+            }
+        });
+    });
     if (e != hipSuccess) return e;
     if (ds && cg_beta_fold_ok(c)) return hipSuccess;  // the next apply takes the betanom step
     if (multi_rank(c)) return launch_fin_sum(c, (int)grid, 1);
     return launch_update_fin(c, (int)ugrid, ds ? c->nblk : 0);
 }
-
 
 // local partial sums of q = A d on the shared interface planes (what the neighbour must add)
 template <int S>

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "cdfem_internal.hpp"
+#include "dispatch.hpp"
 #include "brick_core.hpp"
 #include "pa_core.hpp"
 #include "reduce.hpp"
@@ -357,37 +358,12 @@ hipError_t launch_brick_um(cdfem_ctx *c, const BrickGeom &g, unsigned nbrick_lau
     // the Jacobi scale from the class table (not under pc = none, whose dinv is the ones vector)
     const bool ud = uniform_diag(c) && dinv == c->d_dinv;
     if (ud) dinv = c->d_udiag;
-#define CDFEM_BUM(XF_, BF_, FU_, UD_)                                                                              \
-    do {                                                                                                      \
-        if (whole)                                                                                            \
-            CDFEM_LAUNCH(c, (k_brick_cg<XF_, BF_, FU_, UD_>), grid, block, 0, r, dinv, d_old, d_new, c->d_face,      \
-                         c->d_uelem, c->d_ess, g, c->zlo_shared, dpart, c->d_state, x, upart, nupart, kk,       \
-                         c->d_gsum, c->d_gcnt, c->den_grp, c->nblk);                                            \
-        else                                                                                                  \
-            hipLaunchKernelGGL((k_brick_cg<XF_, BF_, FU_, UD_>), grid, block, 0, s, r, dinv, d_old, d_new, c->d_face, \
-                               c->d_uelem, c->d_ess, g, c->zlo_shared, dpart, c->d_state, x, upart, nupart, kk, \
-                               c->d_gsum, c->d_gcnt, c->den_grp, c->nblk);                                      \
-    } while (0)
-#define CDFEM_BUM3(XF_, BF_, FU_)                                                                             \
-    do {                                                                                                      \
-        if (ud) CDFEM_BUM(XF_, BF_, FU_, true);                                                               \
-        else CDFEM_BUM(XF_, BF_, FU_, false);                                                                 \
-    } while (0)
-#define CDFEM_BUM2(XF_, BF_)                                                                                  \
-    do {                                                                                                      \
-        if (full) CDFEM_BUM3(XF_, BF_, true);                                                                 \
-        else CDFEM_BUM3(XF_, BF_, false);                                                                     \
-    } while (0)
-    if (kk >= 0) {
-        if (x) CDFEM_BUM2(true, true);
-        else CDFEM_BUM2(false, true);
-    } else {
-        if (x) CDFEM_BUM2(true, false);
-        else CDFEM_BUM2(false, false);
-    }
-#undef CDFEM_BUM2
-#undef CDFEM_BUM3
-#undef CDFEM_BUM
+    dispatch_bools(x != nullptr, kk >= 0, full, ud, [&](auto XF, auto BF, auto FU, auto UD) {
+        const auto kern = k_brick_cg<XF(), BF(), FU(), UD()>;
+        CDFEM_LAUNCH_ON(c, whole, s, kern, grid, block, 0, r, dinv, d_old, d_new, c->d_face, c->d_uelem, c->d_ess, g,
+                        c->zlo_shared, dpart, c->d_state, x, upart, nupart, kk, c->d_gsum, c->d_gcnt, c->den_grp,
+                        c->nblk);
+    });
     return hipGetLastError();
 }
 

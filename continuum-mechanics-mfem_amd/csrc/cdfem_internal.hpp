@@ -362,6 +362,15 @@ struct cdfem_ctx {
         }                                                                                                    \
     } while (0)
 
+// A launch that is the whole slab on the context stream (whole) goes through CDFEM_LAUNCH and takes an
+// armed event pair; any other (some layers of the slab, on stream s, which may be the context stream
+// too) is a plain launch and leaves the pair armed.
+#define CDFEM_LAUNCH_ON(c, whole, s, kernel, grid, block, shm, ...)                                          \
+    do {                                                                                                     \
+        if (whole) CDFEM_LAUNCH(c, kernel, grid, block, shm, __VA_ARGS__);                                   \
+        else hipLaunchKernelGGL(kernel, grid, block, shm, s, __VA_ARGS__);                                   \
+    } while (0)
+
 namespace cdfem {
 
 // the high-order tile apply forms the point data from the affine factors; with MFMA stages

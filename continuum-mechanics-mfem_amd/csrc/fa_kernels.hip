@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "cdfem_internal.hpp"
+#include "dispatch.hpp"
 #include "reduce.hpp"
 
 namespace cdfem {
@@ -593,40 +594,37 @@ k_perm_scatter(const int32_t *__restrict__ perm, const double *__restrict__ yp, 
 }
 
 // ---- launchers ---------------------------------------------------------------------------------
+// f(DIM, P) as constants for the simplex spaces: tetrahedra of p = 1, 2, triangles of p = 1, 2, 3
+template <class F>
+static hipError_t dispatch_simplex(const cdfem_ctx *c, F &&f)
+{
+    if (c->p < 1 || c->p > 3) return hipErrorInvalidValue;
+    return dispatch_value<31, 32, 21, 22, 23>(10 * c->dim + c->p, hipErrorInvalidValue, [&](auto DP) {
+        return f(std::integral_constant<int, DP() / 10>{}, std::integral_constant<int, DP() % 10>{});
+    });
+}
+
 hipError_t launch_simplex_elem(cdfem_ctx *c, const double *kq, const double *kmq, double kappa, double alpha,
                                const double *conv, const double *cq, const double *mq, double mass)
 {
     const dim3 g((c->ne + 63) / 64), b(64);
     const double c0 = conv ? conv[0] : 0.0, c1 = conv ? conv[1] : 0.0, c2 = (conv && c->dim == 3) ? conv[2] : 0.0;
-#define CDFEM_SIMPLEX(D, P)                                                                              \
-    hipLaunchKernelGGL((k_simplex_elem<D, P>), g, b, 0, c->stream, c->d_verts, c->ne, c->nq_sd, c->nq_scm, \
-                       c->d_stab, c->kinds, kappa, kq, kmq, alpha, c0, c1, c2, cq, mass, mq, c->d_Ee)
-    if (c->dim == 3 && c->p == 1) CDFEM_SIMPLEX(3, 1);
-    else if (c->dim == 3 && c->p == 2) CDFEM_SIMPLEX(3, 2);
-    else if (c->dim == 2 && c->p == 1) CDFEM_SIMPLEX(2, 1);
-    else if (c->dim == 2 && c->p == 2) CDFEM_SIMPLEX(2, 2);
-    else if (c->dim == 2 && c->p == 3) CDFEM_SIMPLEX(2, 3);
-    else return hipErrorInvalidValue;
-#undef CDFEM_SIMPLEX
-    return hipGetLastError();
+    return dispatch_simplex(c, [&](auto D, auto P) {
+        hipLaunchKernelGGL((k_simplex_elem<D(), P()>), g, b, 0, c->stream, c->d_verts, c->ne, c->nq_sd, c->nq_scm,
+                           c->d_stab, c->kinds, kappa, kq, kmq, alpha, c0, c1, c2, cq, mass, mq, c->d_Ee);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_simplex_lf(cdfem_ctx *c, const double *fq, double *Ye)
 {
     const dim3 g((c->ne + 63) / 64), b(64);
-    if (c->dim == 3 && c->p == 1)
-        hipLaunchKernelGGL((k_simplex_lf<3, 4>), g, b, 0, c->stream, c->d_verts, c->ne, c->nq_lf, c->d_stab_lf, fq, Ye);
-    else if (c->dim == 3 && c->p == 2)
-        hipLaunchKernelGGL((k_simplex_lf<3, 10>), g, b, 0, c->stream, c->d_verts, c->ne, c->nq_lf, c->d_stab_lf, fq, Ye);
-    else if (c->dim == 2 && c->p == 1)
-        hipLaunchKernelGGL((k_simplex_lf<2, 3>), g, b, 0, c->stream, c->d_verts, c->ne, c->nq_lf, c->d_stab_lf, fq, Ye);
-    else if (c->dim == 2 && c->p == 2)
-        hipLaunchKernelGGL((k_simplex_lf<2, 6>), g, b, 0, c->stream, c->d_verts, c->ne, c->nq_lf, c->d_stab_lf, fq, Ye);
-    else if (c->dim == 2 && c->p == 3)
-        hipLaunchKernelGGL((k_simplex_lf<2, 10>), g, b, 0, c->stream, c->d_verts, c->ne, c->nq_lf, c->d_stab_lf, fq, Ye);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
+    return dispatch_simplex(c, [&](auto D, auto P) {
+        constexpr int ND = D() == 3 ? (P() + 1) * (P() + 2) * (P() + 3) / 6 : (P() + 1) * (P() + 2) / 2;  // dofs
+        hipLaunchKernelGGL((k_simplex_lf<D(), ND>), g, b, 0, c->stream, c->d_verts, c->ne, c->nq_lf, c->d_stab_lf, fq,
+                           Ye);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_fa_assemble(cdfem_ctx *c)
@@ -685,37 +683,30 @@ static void spmv_launch(cdfem_ctx *c, const double *vals, const double *x, doubl
         const int nwin = lds_windows(c), per = c->spmv_xcd ? (nwin + 7) / 8 : 0;
         const dim3 g(per ? 8u * (unsigned)per : (unsigned)nwin), b(256);
         const int spw = (int)(c->lds_rows / (64 / c->sell_lpr));
-#define CDFEM_SPMV_LDS(L)                                                                                       \
-    CDFEM_LAUNCH(c, (k_sell_spmv_lds<CG, L>), g, b, (size_t)c->lds_max * sizeof(double), c->d_sptr, c->d_sloc, vals, \
-                 c->d_hptr, c->d_hidx, x, y, c->nslices, (int64_t)c->nl, spw, nwin, per, part, st)
-        if (c->sell_lpr == 4) CDFEM_SPMV_LDS(4);
-        else if (c->sell_lpr == 2) CDFEM_SPMV_LDS(2);
-        else CDFEM_SPMV_LDS(1);
-#undef CDFEM_SPMV_LDS
+        const auto launch = [&](auto L) {
+            const auto kern = k_sell_spmv_lds<CG, L()>;
+            CDFEM_LAUNCH(c, kern, g, b, (size_t)c->lds_max * sizeof(double), c->d_sptr, c->d_sloc, vals, c->d_hptr,
+                         c->d_hidx, x, y, c->nslices, (int64_t)c->nl, spw, nwin, per, part, st);
+            return true;
+        };
+        if (!dispatch_value<4, 2>(c->sell_lpr, false, launch)) launch(std::integral_constant<int, 1>{});
         return;
     }
     const dim3 g(sell_grid(c)), b(256);
     const int per = sell_xcd_per(c);
     const bool perm = c->sell_windowed;
-#define CDFEM_SPMV(CI, PM)                                                                                       \
-    CDFEM_LAUNCH(c, (k_sell_spmv<CG, CI, PM, 4, false, true>), g, b, 0, c->d_sptr, c->d_srows,                     \
-                 (const CI *)(sizeof(CI) == 2 ? (const void *)c->d_sdel : (const void *)c->d_scols), vals, x, y,  \
-                 c->nslices, (int64_t)c->nl, per, part, st, (const int32_t *)nullptr, (const uint8_t *)nullptr)
-#define CDFEM_SPMV_MIX(PM)                                                                                       \
-    CDFEM_LAUNCH(c, (k_sell_spmv<CG, int16_t, PM, 4, false, true, true>), g, b, 0, c->d_sptr, c->d_srows,          \
-                 c->d_sdel, vals, x, y, c->nslices, (int64_t)c->nl, per, part, st, c->d_scols, c->d_swide)
-    if (spmv_delta(c) && c->d_swide) {
-        if (perm) CDFEM_SPMV_MIX(true);
-        else CDFEM_SPMV_MIX(false);
-    } else if (spmv_delta(c)) {
-        if (perm) CDFEM_SPMV(int16_t, true);
-        else CDFEM_SPMV(int16_t, false);
-    } else {
-        if (perm) CDFEM_SPMV(int32_t, true);
-        else CDFEM_SPMV(int32_t, false);
-    }
-#undef CDFEM_SPMV
-#undef CDFEM_SPMV_MIX
+    // 16-bit column deltas (spmv_delta), MIX: with 32-bit columns on the slices d_swide flags
+    const bool i16 = spmv_delta(c), mix = i16 && c->d_swide != nullptr;
+    dispatch_bools(i16, mix, perm, [&](auto I16, auto MIX, auto PM) {
+        if constexpr (I16() || !MIX()) {
+            using CI = std::conditional_t<I16(), int16_t, int32_t>;
+            const auto kern = k_sell_spmv<CG, CI, PM(), 4, false, true, MIX()>;
+            CDFEM_LAUNCH(c, kern, g, b, 0, c->d_sptr, c->d_srows,
+                         (const CI *)(I16() ? (const void *)c->d_sdel : (const void *)c->d_scols), vals, x, y,
+                         c->nslices, (int64_t)c->nl, per, part, st, MIX() ? c->d_scols : (const int32_t *)nullptr,
+                         MIX() ? c->d_swide : (const uint8_t *)nullptr);
+        }
+    });
 }
 
 // y = A x in the mesh's dof order.  Permuted layout: inside a permuted-order solve (perm_space)

@@ -23,6 +23,7 @@
 
 #include "brick_core.hpp"
 #include "cdfem_internal.hpp"
+#include "dispatch.hpp"
 #include "reduce.hpp"
 
 namespace cdfem {
@@ -521,13 +522,12 @@ static void orth_passes(cdfem_ctx *c, double *w, const double *dinv, double *V, 
     const int64_t n = c->nl;
     const bool mr = multi_rank(c);
     const GmPatchSrc src = ps ? *ps : GmPatchSrc{};
-#define CDFEM_P1(S_)                                                                                      \
-    hipLaunchKernelGGL((k_gm_pass1<kGmBatch, EPT, S_>), dim3(nb), dim3(kRedThreads), 0, c->stream, w, dinv, V, n, \
-                       ldv, owned_from(c), part, nb, st, src)
-    if (ps && ps->S == 9) CDFEM_P1(9);
-    else if (ps && ps->S == 5) CDFEM_P1(5);
-    else CDFEM_P1(0);
-#undef CDFEM_P1
+    // (S: the side of the brick patch w is read from, 0: w itself; launch_gm_orth admits 5 and 9)
+    (void)dispatch_value<0, 5, 9>(ps ? ps->S : 0, false, [&](auto S) {
+        hipLaunchKernelGGL((k_gm_pass1<kGmBatch, EPT, S()>), dim3(nb), dim3(kRedThreads), 0, c->stream, w, dinv, V, n,
+                           ldv, owned_from(c), part, nb, st, src);
+        return true;
+    });
     hipLaunchKernelGGL(k_gm_dots_fin_mb, dim3(m + 1), dim3(kRedThreads), 0, c->stream, part, nb, st, mr ? 1 : 0);
     if (mr) {
         comm_allreduce(c, red_of(st), m + 1);
@@ -547,12 +547,11 @@ hipError_t launch_gm_orth(cdfem_ctx *c, double *w, const double *dinv, double *V
                           GmresState *st, int m, GmresState *poll, const GmPatchSrc *ps)
 {
     if (ps && ps->S != 5 && ps->S != 9) return hipErrorInvalidValue;
-    switch (orth_ept(c)) {
-    case 5: orth_passes<5>(c, w, dinv, V, ldv, part, st, m, poll, ps); break;
-    case 6: orth_passes<6>(c, w, dinv, V, ldv, part, st, m, poll, ps); break;
-    case 8: orth_passes<8>(c, w, dinv, V, ldv, part, st, m, poll, ps); break;
-    default: orth_passes<4>(c, w, dinv, V, ldv, part, st, m, poll, ps); break;
-    }
+    const auto run = [&](auto EPT) {
+        orth_passes<EPT()>(c, w, dinv, V, ldv, part, st, m, poll, ps);
+        return true;
+    };
+    if (!dispatch_value<5, 6, 8>(orth_ept(c), false, run)) run(std::integral_constant<int, 4>{});  // (any other: 4)
     return hipGetLastError();
 }
 

@@ -39,6 +39,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cdfem_internal.hpp"
+#include "dispatch.hpp"
 #include "pa_core.hpp"
 #include "reduce.hpp"
 
@@ -693,12 +694,21 @@ static hipError_t ktab_build(cdfem_ctx *c, const Tab<D1, Q1> &T)
     return hipSuccess;
 }
 
+// f(D1, Q1) as constants for p = 3, 4 under the operators' Gauss rule of p + 2 points
+template <class F>
+static hipError_t dispatch_ho(const cdfem_ctx *c, F &&f)
+{
+    if (c->rule_op.q1 != c->p + 2) return hipErrorInvalidValue;
+    return dispatch_value<3, 4>(c->p, hipErrorInvalidValue, [&](auto P) {
+        return f(std::integral_constant<int, P() + 1>{}, std::integral_constant<int, P() + 2>{});
+    });
+}
+
 hipError_t ho_ktab(cdfem_ctx *c, const double **out)
 {
-    const int q1 = c->rule_op.q1;
-    hipError_t e = hipErrorInvalidValue;
-    if (c->p == 3 && q1 == 5) e = ktab_build<4, 5>(c, make_tab<4, 5>(c->rule_op));
-    if (c->p == 4 && q1 == 6) e = ktab_build<5, 6>(c, make_tab<5, 6>(c->rule_op));
+    const hipError_t e = dispatch_ho(c, [&](auto D1, auto Q1) {
+        return ktab_build<D1(), Q1()>(c, make_tab<D1(), Q1()>(c->rule_op));
+    });
     *out = c->d_ktab;
     return e;
 }
@@ -717,37 +727,24 @@ static hipError_t ktile_kinds(cdfem_ctx *c, const double *x, double *Ye, bool co
     geo.nz = c->epencil ? (uint32_t)(c->ne / ((int64_t)geo.ho.nx * geo.ho.ny)) : 0;
     geo.ess = c->d_ess;
     const double *qa = c->d_qaff;
-    double *const np = nullptr;
     {
         const hipError_t e = ktab_build<D1, Q1>(c, T);
         if (e != hipSuccess) return e;
     }
     const double *kt = c->d_ktab;
     if (kt == nullptr) return hipErrorInvalidValue;
-    if (den_part && dnew) {
-        if (!c->epencil || !con || !dold) return hipErrorInvalidValue;
-        CDFEM_LAUNCH(c, (k_apply3d_ktile<D1, Q1, K, true, true, true, true>), grid, block, 0, c->d_map, x, qa, Ye,
-                     T, c->ne, geo, st, den_part, dold, dnew, kt);
-    } else if (den_part) {
-        if (!c->epencil || !con) return hipErrorInvalidValue;
-        CDFEM_LAUNCH(c, (k_apply3d_ktile<D1, Q1, K, true, true, true>), grid, block, 0, c->d_map, x, qa, Ye, T,
-                     c->ne, geo, st, den_part, np, np, kt);
-    } else if (c->epencil) {
-        if (con)
-            CDFEM_LAUNCH(c, (k_apply3d_ktile<D1, Q1, K, true, true, false>), grid, block, 0, c->d_map, x, qa, Ye,
-                         T, c->ne, geo, st, np, np, np, kt);
-        else
-            CDFEM_LAUNCH(c, (k_apply3d_ktile<D1, Q1, K, false, true, false>), grid, block, 0, c->d_map, x, qa, Ye,
-                         T, c->ne, geo, st, np, np, np, kt);
-    } else {
-        if (con)
-            CDFEM_LAUNCH(c, (k_apply3d_ktile<D1, Q1, K, true, false, false>), grid, block, 0, c->d_map, x, qa, Ye,
-                         T, c->ne, geo, st, np, np, np, kt);
-        else
-            CDFEM_LAUNCH(c, (k_apply3d_ktile<D1, Q1, K, false, false, false>), grid, block, 0, c->d_map, x, qa, Ye,
-                         T, c->ne, geo, st, np, np, np, kt);
-    }
-    return hipGetLastError();
+    // den partials (CG mode) need the constrained apply on the element pencils, the direction fold the den
+    const bool den = den_part != nullptr, df = den && dnew != nullptr;
+    if (df && !dold) return hipErrorInvalidValue;
+    return dispatch_bools(con, c->epencil != 0, den, df, [&](auto CON, auto LAT, auto DEN, auto DF) {
+        if constexpr ((DEN() && !(CON() && LAT())) || (DF() && !DEN())) return hipErrorInvalidValue;
+        else {
+            const auto kern = k_apply3d_ktile<D1, Q1, K, CON(), LAT(), DEN(), DF()>;
+            CDFEM_LAUNCH(c, kern, grid, block, 0, c->d_map, x, qa, Ye, T, c->ne, geo, st, den_part,
+                         DF() ? dold : nullptr, DF() ? dnew : nullptr, kt);
+            return hipGetLastError();
+        }
+    });
 }
 
 // the fused CG apply with the direction fold (ho_dfold): d_new = z + beta d_old, Ye = A_c d_new, den
@@ -755,16 +752,8 @@ template <int D1, int Q1>
 static hipError_t ktile_dfold(cdfem_ctx *c, const double *z, const double *dold, double *dnew, double *Ye,
                               const KrylovState *st, double *part)
 {
-    switch (c->kinds) {
-    case 1: return ktile_kinds<D1, Q1, 1>(c, z, Ye, true, st, part, dold, dnew);
-    case 2: return ktile_kinds<D1, Q1, 2>(c, z, Ye, true, st, part, dold, dnew);
-    case 3: return ktile_kinds<D1, Q1, 3>(c, z, Ye, true, st, part, dold, dnew);
-    case 4: return ktile_kinds<D1, Q1, 4>(c, z, Ye, true, st, part, dold, dnew);
-    case 5: return ktile_kinds<D1, Q1, 5>(c, z, Ye, true, st, part, dold, dnew);
-    case 6: return ktile_kinds<D1, Q1, 6>(c, z, Ye, true, st, part, dold, dnew);
-    case 7: return ktile_kinds<D1, Q1, 7>(c, z, Ye, true, st, part, dold, dnew);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_kinds(c->kinds, hipErrorInvalidValue,
+                          [&](auto K) { return ktile_kinds<D1, Q1, K()>(c, z, Ye, true, st, part, dold, dnew); });
 }
 
 template <int D1, int Q1, unsigned K, int MF>
@@ -782,26 +771,15 @@ static hipError_t tile_kinds_mf(cdfem_ctx *c, const double *x, double *Ye, bool 
     geo.ess = c->d_ess;
     const double *qd = (MF & 32) ? c->d_hgeom : (MF & 16) ? c->d_qaff : c->d_qd;
     if (qd == nullptr) return hipErrorInvalidValue;
-    if (den_part) {
-        if (!c->epencil || !con) return hipErrorInvalidValue;
-        CDFEM_LAUNCH(c, (k_apply3d_tile<D1, Q1, K, true, true, true, MF>), grid, block, 0, c->d_map, x, qd,
-                     Ye, T, c->ne, geo, st, den_part);
-    } else if (c->epencil) {
-        if (con)
-            CDFEM_LAUNCH(c, (k_apply3d_tile<D1, Q1, K, true, true, false, MF>), grid, block, 0, c->d_map, x, qd,
-                         Ye, T, c->ne, geo, st, (double *)nullptr);
-        else
-            CDFEM_LAUNCH(c, (k_apply3d_tile<D1, Q1, K, false, true, false, MF>), grid, block, 0, c->d_map, x, qd,
-                         Ye, T, c->ne, geo, st, (double *)nullptr);
-    } else {
-        if (con)
-            CDFEM_LAUNCH(c, (k_apply3d_tile<D1, Q1, K, true, false, false, MF>), grid, block, 0, c->d_map, x, qd,
-                         Ye, T, c->ne, geo, st, (double *)nullptr);
-        else
-            CDFEM_LAUNCH(c, (k_apply3d_tile<D1, Q1, K, false, false, false, MF>), grid, block, 0, c->d_map, x,
-                         qd, Ye, T, c->ne, geo, st, (double *)nullptr);
-    }
-    return hipGetLastError();
+    // den partials (CG mode) need the constrained apply on the element pencils
+    return dispatch_bools(con, c->epencil != 0, den_part != nullptr, [&](auto CON, auto LAT, auto DEN) {
+        if constexpr (DEN() && !(CON() && LAT())) return hipErrorInvalidValue;
+        else {
+            const auto kern = k_apply3d_tile<D1, Q1, K, CON(), LAT(), DEN(), MF>;
+            CDFEM_LAUNCH(c, kern, grid, block, 0, c->d_map, x, qd, Ye, T, c->ne, geo, st, den_part);
+            return hipGetLastError();
+        }
+    });
 }
 
 template <int D1, int Q1, unsigned K>
@@ -812,50 +790,36 @@ static hipError_t tile_kinds(cdfem_ctx *c, const double *x, double *Ye, bool con
     if (tile_affine(c)) {
         // affine factors; on the BASELINE operator (kinds 7) also with the x / x^T stages on the
         // matrix cores (ho_mfma 1, 8, 9: VERDICT r03 item 4, the arithmetic-bound regime)
-        if constexpr (K == 7) {
-            switch (c->ho_mfma) {
-            case 1: return tile_kinds_mf<D1, Q1, K, 17>(c, x, Ye, con, st, den_part);
-            case 8: return tile_kinds_mf<D1, Q1, K, 24>(c, x, Ye, con, st, den_part);
-            case 9: return tile_kinds_mf<D1, Q1, K, 25>(c, x, Ye, con, st, den_part);
-            default: break;
-            }
-        }
-        return tile_kinds_mf<D1, Q1, K, 16>(c, x, Ye, con, st, den_part);
+        // (tile_affine admits no other mask, and none but 0 off kinds 7)
+        return dispatch_value<0, 1, 8, 9>(c->ho_mfma, hipErrorInvalidValue, [&](auto M) {
+            if constexpr (M() != 0 && K != 7) return hipErrorInvalidValue;
+            else return tile_kinds_mf<D1, Q1, K, 16 + M()>(c, x, Ye, con, st, den_part);
+        });
     }
     // geometric factors formed in the apply (ho_geom: any hex, constant coefficients, ho_mfma 0)
     if (ho_geom_on(c)) return tile_kinds_mf<D1, Q1, K, 32>(c, x, Ye, con, st, den_part);
-    switch (c->ho_mfma) {
-    case 1: return tile_kinds_mf<D1, Q1, K, 1>(c, x, Ye, con, st, den_part);
-    case 3: return tile_kinds_mf<D1, Q1, K, 3>(c, x, Ye, con, st, den_part);
-    case 8: return tile_kinds_mf<D1, Q1, K, 8>(c, x, Ye, con, st, den_part);
-    case 9: return tile_kinds_mf<D1, Q1, K, 9>(c, x, Ye, con, st, den_part);
-    case 15: return tile_kinds_mf<D1, Q1, K, 15>(c, x, Ye, con, st, den_part);
-    default: return tile_kinds_mf<D1, Q1, K, 0>(c, x, Ye, con, st, den_part);
-    }
+    // the stream, with the stages of the mask on the matrix cores; any other mask runs the plain stages
+    hipError_t e = hipSuccess;
+    const bool masked = dispatch_value<1, 3, 8, 9, 15>(c->ho_mfma, false, [&](auto M) {
+        e = tile_kinds_mf<D1, Q1, K, M()>(c, x, Ye, con, st, den_part);
+        return true;
+    });
+    return masked ? e : tile_kinds_mf<D1, Q1, K, 0>(c, x, Ye, con, st, den_part);
 }
 
-template <int D1, int Q1>
+// the tile apply of x (CG mode, den_part: with the den partials, one per block)
 static hipError_t tile_dq(cdfem_ctx *c, const double *x, double *Ye, bool con, const KrylovState *st,
                           double *den_part)
 {
-    switch (c->kinds) {
-    case 1: return tile_kinds<D1, Q1, 1>(c, x, Ye, con, st, den_part);
-    case 2: return tile_kinds<D1, Q1, 2>(c, x, Ye, con, st, den_part);
-    case 3: return tile_kinds<D1, Q1, 3>(c, x, Ye, con, st, den_part);
-    case 4: return tile_kinds<D1, Q1, 4>(c, x, Ye, con, st, den_part);
-    case 5: return tile_kinds<D1, Q1, 5>(c, x, Ye, con, st, den_part);
-    case 6: return tile_kinds<D1, Q1, 6>(c, x, Ye, con, st, den_part);
-    case 7: return tile_kinds<D1, Q1, 7>(c, x, Ye, con, st, den_part);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_ho(c, [&](auto D1, auto Q1) {
+        return dispatch_kinds(c->kinds, hipErrorInvalidValue,
+                              [&](auto K) { return tile_kinds<D1(), Q1(), K()>(c, x, Ye, con, st, den_part); });
+    });
 }
 
 hipError_t launch_apply_wpe(cdfem_ctx *c, const double *x, double *Ye, bool con, const KrylovState *st)
 {
-    const int q1 = c->rule_op.q1;
-    if (c->p == 3 && q1 == 5) return tile_dq<4, 5>(c, x, Ye, con, st, nullptr);
-    if (c->p == 4 && q1 == 6) return tile_dq<5, 6>(c, x, Ye, con, st, nullptr);
-    return hipErrorInvalidValue;
+    return tile_dq(c, x, Ye, con, st, nullptr);
 }
 
 // den partials of the CG-mode tile apply: one per block of the kernel the configuration launches, or
@@ -878,19 +842,13 @@ hipError_t launch_apply_den_dfold(cdfem_ctx *c, const double *z, const double *d
                                   const KrylovState *st, double *part)
 {
     if (!tile_dfold_ok(c)) return hipErrorInvalidValue;
-    const int q1 = c->rule_op.q1;
-    if (c->p == 3 && q1 == 5) return ktile_dfold<4, 5>(c, z, dold, dnew, Ye, st, part);
-    if (c->p == 4 && q1 == 6) return ktile_dfold<5, 6>(c, z, dold, dnew, Ye, st, part);
-    return hipErrorInvalidValue;
+    return dispatch_ho(c, [&](auto D1, auto Q1) { return ktile_dfold<D1(), Q1()>(c, z, dold, dnew, Ye, st, part); });
 }
 
 // CG mode: Ye = A_c d (E-vector) and the den partials (one per block) into part
 hipError_t launch_apply_den(cdfem_ctx *c, const double *d, double *Ye, const KrylovState *st, double *part)
 {
-    const int q1 = c->rule_op.q1;
-    if (c->p == 3 && q1 == 5) return tile_dq<4, 5>(c, d, Ye, true, st, part);
-    if (c->p == 4 && q1 == 6) return tile_dq<5, 6>(c, d, Ye, true, st, part);
-    return hipErrorInvalidValue;
+    return tile_dq(c, d, Ye, true, st, part);
 }
 
 }  // namespace cdfem

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cdfem_internal.hpp"
+#include "dispatch.hpp"
 #include "pa_core.hpp"
 
 namespace cdfem {
@@ -825,19 +826,10 @@ static bool diag_ho_kinds(cdfem_ctx *c, double *Ye)
     constexpr int EPB = 256 / (Q1 * Q1);
     const dim3 g((unsigned)((c->ne + EPB - 1) / EPB)), bs(256);
     const Tab<D1, Q1> T = make_tab<D1, Q1>(c->rule_op);
-#define CDFEM_DHO(K_)                                                                                    \
-    hipLaunchKernelGGL((k_diag_ho<D1, Q1, K_>), g, bs, 0, c->stream, c->d_qd, c->ne, ho_layout(c), T, Ye)
-    switch (c->kinds) {
-    case 1: CDFEM_DHO(1); return true;
-    case 2: CDFEM_DHO(2); return true;
-    case 3: CDFEM_DHO(3); return true;
-    case 4: CDFEM_DHO(4); return true;
-    case 5: CDFEM_DHO(5); return true;
-    case 6: CDFEM_DHO(6); return true;
-    case 7: CDFEM_DHO(7); return true;
-    default: return false;
-    }
-#undef CDFEM_DHO
+    return dispatch_kinds(c->kinds, false, [&](auto K) {
+        hipLaunchKernelGGL((k_diag_ho<D1, Q1, K()>), g, bs, 0, c->stream, c->d_qd, c->ne, ho_layout(c), T, Ye);
+        return true;
+    });
 }
 
 template <int DIM, int D1, int Q1>
@@ -847,20 +839,11 @@ static bool diag_sf_kinds(cdfem_ctx *c, double *Ye)
     const int64_t n = npos * (DIM == 3 ? D1 * D1 : D1);
     const dim3 g(grid_for(n, 256)), bs(256);
     const Tab<D1, Q1> T = make_tab<D1, Q1>(c->rule_op);
-#define CDFEM_DSF(K_)                                                                                      \
-    hipLaunchKernelGGL((k_diag_sf<DIM, D1, Q1, K_>), g, bs, 0, c->stream, c->d_qd, c->d_perm, c->ne, c->nblk, \
-                       c->qlay, ho_layout(c), T, Ye)
-    switch (c->kinds) {
-    case 1: CDFEM_DSF(1); return true;
-    case 2: CDFEM_DSF(2); return true;
-    case 3: CDFEM_DSF(3); return true;
-    case 4: CDFEM_DSF(4); return true;
-    case 5: CDFEM_DSF(5); return true;
-    case 6: CDFEM_DSF(6); return true;
-    case 7: CDFEM_DSF(7); return true;
-    default: return false;
-    }
-#undef CDFEM_DSF
+    return dispatch_kinds(c->kinds, false, [&](auto K) {
+        hipLaunchKernelGGL((k_diag_sf<DIM, D1, Q1, K()>), g, bs, 0, c->stream, c->d_qd, c->d_perm, c->ne, c->nblk,
+                           c->qlay, ho_layout(c), T, Ye);
+        return true;
+    });
 }
 
 hipError_t launch_diag_elem(cdfem_ctx *c, double *Ye)
@@ -868,17 +851,13 @@ hipError_t launch_diag_elem(cdfem_ctx *c, double *Ye)
     const int d1 = c->rule_op.d1, q1 = c->rule_op.q1;
     bool done = false;
     if (d1 == q1 - 1) {  // the operators' Gauss n = p + 2 rules: sum-factorised, compile-time sizes
-        if (c->dim == 3) {
-            if (d1 == 2) done = diag_sf_kinds<3, 2, 3>(c, Ye);
-            else if (d1 == 3) done = diag_sf_kinds<3, 3, 4>(c, Ye);
-            else if (d1 == 4) done = c->qlay == 1 ? diag_ho_kinds<4, 5>(c, Ye) : diag_sf_kinds<3, 4, 5>(c, Ye);
-            else if (d1 == 5) done = c->qlay == 1 ? diag_ho_kinds<5, 6>(c, Ye) : diag_sf_kinds<3, 5, 6>(c, Ye);
-        } else {
-            if (d1 == 2) done = diag_sf_kinds<2, 2, 3>(c, Ye);
-            else if (d1 == 3) done = diag_sf_kinds<2, 3, 4>(c, Ye);
-            else if (d1 == 4) done = diag_sf_kinds<2, 4, 5>(c, Ye);
-            else if (d1 == 5) done = diag_sf_kinds<2, 5, 6>(c, Ye);
-        }
+        done = dispatch_value<2, 3, 4, 5>(d1, false, [&](auto D1) {
+            if (c->dim != 3) return diag_sf_kinds<2, D1(), D1() + 1>(c, Ye);
+            if constexpr (D1() >= 4) {  // p = 3, 4 in the element-major layout: the tile kernel
+                if (c->qlay == 1) return diag_ho_kinds<D1(), D1() + 1>(c, Ye);
+            }
+            return diag_sf_kinds<3, D1(), D1() + 1>(c, Ye);
+        });
     }
     if (done) return hipGetLastError();
     // any other rule: the per-entry quadrature loop
@@ -904,50 +883,28 @@ hipError_t launch_lf_elem(cdfem_ctx *c, const double *d_fq, double *Ye)
     return hipGetLastError();
 }
 
-template <int DIM, int D1, int Q1, unsigned K>
-static hipError_t apply_kinds(cdfem_ctx *c, const double *x, double *Ye, bool con,
-                              const KrylovState *st)
-{
-    const Tab<D1, Q1> T = make_tab<D1, Q1>(c->rule_op);
-    const dim3 grid(grid_for(c->nblk, 4)), block(256);
-    if constexpr (DIM == 3) {
-        const int af = pa_form(c);
-        const double *qd = af == 3 ? c->d_geom : af ? c->d_qaff : c->d_qd;
-#define CDFEM_A3(CON_, AF_)                                                                                  \
-    hipLaunchKernelGGL((k_apply3d<D1, Q1, K, CON_, AF_>), grid, block, 0, c->stream, c->d_map, x, qd, Ye, T, \
-                       c->nblk, st)
-        if (con) {
-            if (af == 3) CDFEM_A3(true, 3); else if (af == 2) CDFEM_A3(true, 2); else if (af == 1) CDFEM_A3(true, 1);
-            else CDFEM_A3(true, 0);
-        } else {
-            if (af == 3) CDFEM_A3(false, 3); else if (af == 2) CDFEM_A3(false, 2); else if (af == 1) CDFEM_A3(false, 1);
-            else CDFEM_A3(false, 0);
-        }
-#undef CDFEM_A3
-    } else {
-        if (con)
-            hipLaunchKernelGGL((k_apply2d<D1, Q1, K, true>), grid, block, 0, c->stream, c->d_map, x,
-                               c->d_qd, Ye, T, c->nblk, st);
-        else
-            hipLaunchKernelGGL((k_apply2d<D1, Q1, K, false>), grid, block, 0, c->stream, c->d_map,
-                               x, c->d_qd, Ye, T, c->nblk, st);
-    }
-    return hipGetLastError();
-}
-
 template <int DIM, int D1, int Q1>
 static hipError_t apply_dq(cdfem_ctx *c, const double *x, double *Ye, bool con, const KrylovState *st)
 {
-    switch (c->kinds) {
-    case 1: return apply_kinds<DIM, D1, Q1, 1>(c, x, Ye, con, st);
-    case 2: return apply_kinds<DIM, D1, Q1, 2>(c, x, Ye, con, st);
-    case 3: return apply_kinds<DIM, D1, Q1, 3>(c, x, Ye, con, st);
-    case 4: return apply_kinds<DIM, D1, Q1, 4>(c, x, Ye, con, st);
-    case 5: return apply_kinds<DIM, D1, Q1, 5>(c, x, Ye, con, st);
-    case 6: return apply_kinds<DIM, D1, Q1, 6>(c, x, Ye, con, st);
-    case 7: return apply_kinds<DIM, D1, Q1, 7>(c, x, Ye, con, st);
-    default: return hipErrorInvalidValue;
-    }
+    const Tab<D1, Q1> T = make_tab<D1, Q1>(c->rule_op);
+    const dim3 grid(grid_for(c->nblk, 4)), block(256);
+    const int af = DIM == 3 ? pa_form(c) : 0;
+    const double *qd = af == 3 ? c->d_geom : af ? c->d_qaff : c->d_qd;
+    return dispatch_kinds(c->kinds, hipErrorInvalidValue, [&](auto K) {
+        return dispatch_bools(con, [&](auto CON) {
+            if constexpr (DIM == 3) {
+                return dispatch_value<0, 1, 2, 3>(af, hipErrorInvalidValue, [&](auto AF) {
+                    hipLaunchKernelGGL((k_apply3d<D1, Q1, K(), CON(), AF()>), grid, block, 0, c->stream, c->d_map, x,
+                                       qd, Ye, T, c->nblk, st);
+                    return hipGetLastError();
+                });
+            } else {
+                hipLaunchKernelGGL((k_apply2d<D1, Q1, K(), CON()>), grid, block, 0, c->stream, c->d_map, x, qd, Ye,
+                                   T, c->nblk, st);
+                return hipGetLastError();
+            }
+        });
+    });
 }
 
 bool apply_supported(int dim, int p)
@@ -961,17 +918,15 @@ bool apply_supported(int dim, int p)
 hipError_t launch_apply_st(cdfem_ctx *c, const double *x, double *Ye, bool con, const KrylovState *st)
 {
     const int q1 = c->rule_op.q1;
-    if (c->dim == 3) {
-        if (c->p == 1 && q1 == 3) return apply_dq<3, 2, 3>(c, x, Ye, con, st);
-        if (c->p == 2 && q1 == 4) return apply_dq<3, 3, 4>(c, x, Ye, con, st);
+    if (c->dim == 3) {  // the Gauss rule of p + 2 points; p = 3, 4: wave per element (ho_kernels.hip)
         if (c->p >= 3) return launch_apply_wpe(c, x, Ye, con, st);
-    } else {
-        if (c->p == 1 && q1 == 2) return apply_dq<2, 2, 2>(c, x, Ye, con, st);
-        if (c->p == 2 && q1 == 3) return apply_dq<2, 3, 3>(c, x, Ye, con, st);
-        if (c->p == 3 && q1 == 4) return apply_dq<2, 4, 4>(c, x, Ye, con, st);
-        if (c->p == 4 && q1 == 5) return apply_dq<2, 5, 5>(c, x, Ye, con, st);
+        if (q1 != c->p + 2) return hipErrorInvalidValue;
+        return dispatch_value<1, 2>(c->p, hipErrorInvalidValue,
+                                    [&](auto P) { return apply_dq<3, P() + 1, P() + 2>(c, x, Ye, con, st); });
     }
-    return hipErrorInvalidValue;
+    if (q1 != c->p + 1) return hipErrorInvalidValue;  // 2D: p + 1 points
+    return dispatch_value<1, 2, 3, 4>(c->p, hipErrorInvalidValue,
+                                      [&](auto P) { return apply_dq<2, P() + 1, P() + 1>(c, x, Ye, con, st); });
 }
 
 hipError_t launch_apply(cdfem_ctx *c, const double *x, double *Ye, bool constrained)
