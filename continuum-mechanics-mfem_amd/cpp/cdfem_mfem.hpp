@@ -2312,9 +2312,17 @@ private:
     int kdim = 30;
 };
 
+// BiCGStab with PETSc KSPBCGS semantics (left preconditioning, ||M^-1 r|| <= max(rtol ||M^-1 b||, atol));
+// not MFEM's BiCGSTABSolver, whose stopping rules differ
+class PetscBCGSSolver : public IterativeSolver {
+public:
+    using IterativeSolver::IterativeSolver;
+    void Mult(const Vector &b, Vector &x) const override { Run(CDFEM_BICGSTAB, 0, b, x); }
+};
+
 // ---- PETSc-named front end (linear_convection_diffusion_2D.cpp:268-282, :364-375) --------------
 // MFEMInitializePetsc reads an options file with the keys the reference's Input/*.opts set:
-// -ksp_type {gmres, cg}, -ksp_rtol, -ksp_atol, -ksp_max_it, -ksp_gmres_restart, -pc_type
+// -ksp_type {gmres, cg, bcgs}, -ksp_rtol, -ksp_atol, -ksp_max_it, -ksp_gmres_restart, -pc_type
 // {jacobi, none, ilu, bjacobi with -sub_ksp_type preonly -sub_pc_type ilu}.  A solver with an options
 // prefix reads "-<prefix><key>" (Input/petsc_nonlinear.opts: -newton_ls_ksp_rtol ...).  Absent keys
 // take PETSc's defaults: gmres, restart 30, rtol 1e-5, atol 1e-50, max_it 10000, and PETSc's default
@@ -2448,7 +2456,9 @@ private:
             auto g = std::make_unique<GMRESSolver>();
             g->SetKDim(std::stoi(Opt("ksp_gmres_restart", "30")));
             solver_ = std::move(g);
-        } else
+        } else if (type == "bcgs")
+            solver_ = std::make_unique<PetscBCGSSolver>();
+        else
             throw std::invalid_argument("unsupported -" + prefix_ + "ksp_type " + type);
         solver_->SetRelTol(rel_ >= 0 ? rel_ : std::stod(Opt("ksp_rtol", "1e-5")));
         solver_->SetAbsTol(abs_ >= 0 ? abs_ : std::stod(Opt("ksp_atol", "1e-50")));

@@ -130,6 +130,8 @@ void free_mesh(cdfem_ctx *c)
     dfree(c->d_ess); dfree(c->d_ess_list); dfree(c->d_qd); dfree(c->d_qaff); dfree(c->d_geom); dfree(c->d_hgeom); dfree(c->d_Ye); dfree(c->d_dinv);
     for (auto &w : c->d_w) dfree(w);
     dfree(c->d_part); dfree(c->d_tpart); dfree(c->d_gm); dfree(c->d_gm_part); dfree(c->d_ktab);
+    dfree(c->d_bcgs); dfree(c->d_bcgs_part);
+    c->bcgs_n = -1;
     c->ktab_key = -1;  // rebuilt (and reallocated) by the next k_apply3d_ktile launch
     dfree(c->d_perm); dfree(c->d_face); dfree(c->d_ones); dfree(c->d_dalt);
     for (auto &b : c->d_if) dfree(b);
@@ -848,6 +850,128 @@ void solve_gmres(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, d
     HIPCHK(hipMemcpyAsync(dX, x, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
 }
 
+// PETSc KSPBCGS + left preconditioning on the constrained operator (bicgstab.hip): seven L-vectors, two
+// operator applies per iteration, no orthogonalisation.  The host queues iterations without waiting
+// for the device: every check_every-th iteration's last scalar kernel posts the head of the state into
+// the pinned slot (i / check_every) % kBcgsSlots, a function of the iteration number alone and so the
+// same on every rank, and the host reads a posted iteration's slot one check later, after the next
+// check_every iterations are queued (the lag-one poll of solve_gmres).  A slot is rewritten kBcgsSlots
+// checks later, after the host has read it, so a check reads the state of exactly the iteration it names;
+// the all-reduced sums make that state the same on every rank, so every rank leaves the loop at the same
+// iteration and their collectives pair up.  Past the stop every solver kernel exits at entry; the applies
+// do not check: a stop at iteration s is posted by the next polled iteration q < s + check_every and read
+// after iteration q + check_every is queued, so at most 2 check_every - 1 iterations, that is
+// 2 (2 check_every - 1) operator applies, run past the stop (and never more than max_iter iterations in all).
+void solve_bicgstab(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, double *dX,
+                    cdfem_solver_result &res)
+{
+    const int64_t n = c->nl;
+    const int64_t ldv = (n + 31) / 32 * 32;  // every vector on a 256-byte boundary
+    const int nb = bcgs_blocks(n);
+    if (c->bcgs_n != n || !c->d_bcgs) {
+        dfree(c->d_bcgs);
+        dfree(c->d_bcgs_part);
+        c->d_bcgs = dalloc<double>((size_t)6 * ldv);
+        c->d_bcgs_part = dalloc<double>((size_t)3 * nb);
+        c->bcgs_n = n;
+    }
+    if (!c->d_bcst) {
+        HIPCHK(hipMalloc(&c->d_bcst, sizeof(BcgsState)));
+        HIPCHK(hipHostMalloc(&c->h_bcpoll, (kBcgsSlots + 1) * sizeof(BcgsState), hipHostMallocDefault));
+        for (auto &e : c->bc_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    const double *dinv = nullptr;
+    const bool ilu = p.pc == CDFEM_PC_ILU;
+    if (p.pc == CDFEM_PC_JACOBI) {
+        dinv = solver_dinv(c);
+    } else if (ilu) {
+        if (!c->fa_ready) throw UnsupportedError("ILU(0) needs an assembled operator (cdfem_fa_setup)");
+        if (multi_rank(c) && c->part_mode != 2)
+            throw UnsupportedError("block-Jacobi ILU(0) needs a general partition (cdfem_set_shared)");
+        ilu_setup(c);
+    }
+    double *x = c->d_bcgs, *r = x + ldv, *rh = r + ldv, *pv = rh + ldv, *v = pv + ldv, *t = v + ldv;
+    double *w = c->d_w[4], *part = c->d_bcgs_part;  // w: the apply's output (and ilu_apply's input)
+    BcgsState *st = c->d_bcst, *poll = c->h_bcpoll;
+    // one rank on the structured patch-buffer Mult: k_bcgs_v / k_bcgs_t form A_c u from the patch buffer
+    // itself (GMRES's predicate, set_option "gm_pb")
+    const bool gpb = c->gm_pb != 0 && !ilu && !multi_rank(c) && use_brick(c) && brick_mult_pb_on(c);
+    c->bcgs_src = gpb ? kBrick * c->p + 1 : 0;
+    c->bcgs_diag = dinv ? 1 : 0;
+    const int ce = p.check_every > 0 ? p.check_every : 16;
+    // w = A_c u, or phase 1 of the structured Mult alone (the patch buffer is the result); then M^{-1}
+    auto mult = [&](const double *u) -> const double * {
+        if (gpb) {
+            prof_mark(c, CDFEM_K_APPLY, true);
+            HIPCHK(launch_brick_mult(c, u, w, true, 1));
+            prof_mark(c, CDFEM_K_APPLY, false);
+            return w;
+        }
+        op_apply_global(c, u, w, true);
+        if (!ilu) return w;
+        HIPCHK(ilu_apply(c));  // ilu.z = (LU)^{-1} w
+        return c->ilu.z;
+    };
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipMemsetAsync(x, 0, n * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(pv, 0, n * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(v, 0, n * sizeof(double), c->stream));
+    const double *b0 = dB;
+    if (ilu) {  // r = (LU)^{-1} B
+        HIPCHK(hipMemcpyAsync(w, dB, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(ilu_apply(c));
+        b0 = c->ilu.z;
+    }
+    prof_mark(c, CDFEM_K_UPDATE, true);
+    HIPCHK(launch_bcgs_init(c, b0, dinv, r, rh, part, st, p.rel_tol, p.abs_tol, p.max_iter, &poll[kBcgsSlots]));
+    prof_mark(c, CDFEM_K_UPDATE, false);
+    HIPCHK(hipEventRecord(c->bc_ev[0], c->stream));
+    HIPCHK(hipEventSynchronize(c->bc_ev[0]));
+    int nchecks = 0, prev_slot = -1;
+    for (int i = 0; i < p.max_iter && !poll[kBcgsSlots].done; ++i) {
+        const bool polled = (i + 1) % ce == 0;
+        const int slot = (i / ce) % kBcgsSlots;
+        prof_mark(c, CDFEM_K_UPDATE, true);
+        HIPCHK(launch_bcgs_p(c, r, pv, v, st));
+        prof_mark(c, CDFEM_K_UPDATE, false);
+        const double *ap = mult(pv);
+        const GmPatchSrc srcp = gpb ? gm_patch_src(c, pv) : GmPatchSrc{};
+        prof_mark(c, CDFEM_K_UPDATE, true);
+        HIPCHK(launch_bcgs_v(c, ap, dinv, rh, v, r, part, st, gpb ? &srcp : nullptr));
+        prof_mark(c, CDFEM_K_UPDATE, false);
+        const double *as = mult(r);
+        const GmPatchSrc srcs = gpb ? gm_patch_src(c, r) : GmPatchSrc{};
+        prof_mark(c, CDFEM_K_UPDATE, true);
+        HIPCHK(launch_bcgs_t(c, as, dinv, x, pv, r, t, rh, part, st, polled ? &poll[slot] : nullptr,
+                             gpb ? &srcs : nullptr));
+        prof_mark(c, CDFEM_K_UPDATE, false);
+        if (!polled) continue;
+        HIPCHK(hipEventRecord(c->bc_ev[nchecks & 1], c->stream));
+        const int prev = prev_slot;
+        prev_slot = slot;
+        ++nchecks;
+        if (prev < 0) continue;
+        HIPCHK(hipEventSynchronize(c->bc_ev[nchecks & 1]));  // the previous check's event
+        if (poll[prev].done) break;                           // exactly its iteration's state
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    prof_collect(c);
+    BcgsState fin{};
+    HIPCHK(hipMemcpy(&fin, st, sizeof(BcgsState), hipMemcpyDeviceToHost));
+    res.converged = fin.converged;
+    res.iterations = fin.its;
+    res.initial_norm = fin.res0;
+    res.final_norm = fin.dp;
+    res.seconds = std::chrono::duration<double>(t1 - t0).count();
+    if (fin.breakdown)
+        c->err = fin.breakdown == kBcgsBreakRho  ? "BiCGStab breakdown: rho = (r, rh) is zero"
+                 : fin.breakdown == kBcgsBreakD1 ? "BiCGStab breakdown: (v, rh) is zero"
+                                                 : "BiCGStab breakdown: (t, t) is zero with a nonzero s";
+    HIPCHK(hipMemcpyAsync(dX, x, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+}
+
 }  // namespace
 
 // ho_uniform: the block CG applies the common element matrix on the matrix cores (k_hobrick_um); the
@@ -909,6 +1033,10 @@ void cdfem_destroy(cdfem_ctx *c)
     if (c->d_gmst) (void)hipFree(c->d_gmst);
     if (c->h_gmpoll) (void)hipHostFree(c->h_gmpoll);
     for (auto e : c->gm_ev)
+        if (e) (void)hipEventDestroy(e);
+    if (c->d_bcst) (void)hipFree(c->d_bcst);
+    if (c->h_bcpoll) (void)hipHostFree(c->h_bcpoll);
+    for (auto e : c->bc_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &s : c->prof)
         for (auto e : s.ev) (void)hipEventDestroy(e);
@@ -1808,10 +1936,12 @@ int cdfem_solve(cdfem_ctx *c, const cdfem_solver_params *p, const double *B, dou
         if (p->max_iter < 0) throw ArgError("max_iter < 0");
         if (p->pc != CDFEM_PC_NONE && p->pc != CDFEM_PC_JACOBI && p->pc != CDFEM_PC_ILU)
             throw ArgError("unknown preconditioner");
-        if (p->pc == CDFEM_PC_ILU && p->method != CDFEM_GMRES)
+        if (p->pc == CDFEM_PC_ILU && p->method == CDFEM_CG)
             throw UnsupportedError("ILU(0) preconditions GMRES (a nonsymmetric preconditioner for CG)");
         *res = cdfem_solver_result{};
-        if (p->method != CDFEM_CG && p->method != CDFEM_GMRES) throw ArgError("unknown method");
+        if (p->method != CDFEM_CG && p->method != CDFEM_GMRES && p->method != CDFEM_BICGSTAB)
+            throw ArgError("unknown method");
+        c->last_method = p->method;
         const double *dB = dev_in(c, B, where, c->d_w[6], c->nl);
         double *dX = where == CDFEM_DEVICE ? X : c->d_w[1];
         // permuted SpMV layout (sell_plan.cpp): the Krylov iteration runs in the SpMV's order, B in
@@ -1835,6 +1965,8 @@ int cdfem_solve(cdfem_ctx *c, const cdfem_solver_params *p, const double *B, dou
                 solve_cg_brick(c, *p, dBs, dXs, *res);
             else
                 solve_cg(c, *p, dBs, dXs, *res);
+        } else if (p->method == CDFEM_BICGSTAB) {
+            solve_bicgstab(c, *p, dBs, dXs, *res);
         } else {
             solve_gmres(c, *p, dBs, dXs, *res);
         }
@@ -2084,6 +2216,11 @@ int cdfem_kernel_name(cdfem_ctx *c, int k, char *buf, size_t n)
     return guarded(c, [&] {
         require_pa(c);
         if (!buf || n == 0) throw ArgError("buffer is null");
+        if (k == CDFEM_K_UPDATE && c->last_method == CDFEM_BICGSTAB) {
+            // the last BiCGStab solve's operator source: the Mult's output (S=0) or the patch buffer (S=4p+1)
+            std::snprintf(buf, n, "k_bcgs_v<S=%d>", c->bcgs_src);
+            return CDFEM_OK;
+        }
         if (k != CDFEM_K_APPLY) throw UnsupportedError("kernel names: the operator apply only");
         const char *name = c->fa_ready ? (c->lds_rows > 0 ? "k_sell_spmv_lds" : "k_sell_spmv")
                            : use_brick(c) ? "k_brick_cg"
@@ -2187,6 +2324,18 @@ int cdfem_kernel_bytes(cdfem_ctx *c, int k, double *bytes)
         require_pa(c);
         if (!bytes) throw ArgError("bytes is null");
         const double nl = (double)c->nl, ne = (double)c->ne, nd = c->nd;
+        if (k == CDFEM_K_UPDATE && c->last_method == CDFEM_BICGSTAB) {
+            // the five vector kernels of one BiCGStab iteration (bicgstab.hip): k_bcgs_p 4 N, k_bcgs_s 3 N,
+            // k_bcgs_x 7 N doubles; k_bcgs_v and k_bcgs_t each write their vector and read rh (s) and the
+            // diagonal when there is one (2 or 3 N), plus the apply's result: the output vector (N), or with
+            // the patch source the patch buffer, the essential flags and the apply's input on the essential
+            // rows (counted as the flags: the rows are few)
+            const double diag = c->bcgs_diag ? 1.0 : 0.0;
+            const double S = kBrick * c->p + 1.0;
+            const double src = c->bcgs_src ? 8.0 * S * S * S * (double)c->nblk + 1.0 * nl : 8.0 * nl;
+            *bytes = 8.0 * nl * (4 + 3 + 7) + 2.0 * (8.0 * nl * (2.0 + diag) + src);
+            return CDFEM_OK;
+        }
         if (c->fa_ready) {  // CSR SpMV: values + columns + row pointers + x + y
             if (k != CDFEM_K_APPLY) throw ArgError("FA operators report the SpMV (CDFEM_K_APPLY) only");
             // (SELL adds < 1 % padding; 16-bit column deltas when the bandwidth fits)

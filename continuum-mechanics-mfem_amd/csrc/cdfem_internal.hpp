@@ -94,6 +94,18 @@ struct GmresState {
 };
 constexpr size_t kGmPollBytes = 32;
 
+// Device-side BiCGStab state (bicgstab.hip).  The first 24 bytes are what the host polls.
+enum : int { kBcgsBreakRho = 1, kBcgsBreakD1 = 2, kBcgsBreakD2 = 3 };  // BcgsState::breakdown
+constexpr int kBcgsSlots = 4;  // pinned poll slots of the iterations, + 1 for the start
+struct BcgsState {
+    int done, converged, its, breakdown;
+    double dp;
+    // ----
+    int half, max_it;              // half: d2 == 0, the x update adds alpha p alone and the solve ends
+    double ttol, res0, rho, alpha, omega, beta, ss;
+    double red[4];                 // multi-rank: rank-local sums awaiting the all-reduce
+};
+
 // ILU(0) preconditioner state (ilu_kernels.hip)
 struct IluState {
     bool ready = false;
@@ -338,6 +350,17 @@ struct cdfem_ctx {
     cdfem::GmresState *d_gmst = nullptr;   // device GMRES state
     cdfem::GmresState *h_gmpoll = nullptr; // pinned, 2 poll slots of kGmPollBytes
     hipEvent_t gm_ev[2] = {};
+    double *d_bcgs = nullptr;           // BiCGStab vectors x, r, rh, p, v, t (6 * padded nl), allocated by the first solve
+    int64_t bcgs_n = -1;                // the nl d_bcgs and d_bcgs_part were sized for
+    double *d_bcgs_part = nullptr;      // BiCGStab partials [3 * blocks]
+    cdfem::BcgsState *d_bcst = nullptr;    // device BiCGStab state
+    cdfem::BcgsState *h_bcpoll = nullptr;  // pinned, kBcgsSlots + 1 poll slots
+    hipEvent_t bc_ev[2] = {};
+    int last_method = -1;               // method of the last cdfem_solve (kernel_bytes / kernel_name of CDFEM_K_UPDATE)
+    int bcgs_src = 0;                   // the last BiCGStab solve's operator source: 0 the Mult's output, else the patch side
+    int bcgs_diag = 0;                  // the last BiCGStab solve read a Jacobi diagonal
+    int bcgs_ept_auto = 4;              // BiCGStab vector kernels' entries per thread for vectors of bcgs_ept_n entries
+    int64_t bcgs_ept_n = -1;
 
     // profiling
     bool profile = false;
@@ -618,6 +641,17 @@ struct GmPatchSrc;
 hipError_t launch_gm_orth(cdfem_ctx *c, double *w, const double *dinv, double *V, int64_t ldv, double *part,
                           GmresState *st, int m, GmresState *poll, const GmPatchSrc *ps = nullptr);
 hipError_t launch_gm_update(cdfem_ctx *c, double *x, const double *V, int64_t ldv, GmresState *st, GmresState *poll);
+
+// BiCGStab (bicgstab.hip); ps as for launch_gm_orth: k_bcgs_v / k_bcgs_t read the patch buffer instead of w
+int bcgs_blocks(int64_t n);
+hipError_t launch_bcgs_init(cdfem_ctx *c, const double *b, const double *dinv, double *r, double *rh, double *part,
+                            BcgsState *st, double rtol, double atol, int max_it, BcgsState *poll);
+hipError_t launch_bcgs_p(cdfem_ctx *c, const double *r, double *p, const double *v, BcgsState *st);
+hipError_t launch_bcgs_v(cdfem_ctx *c, const double *w, const double *dinv, const double *rh, double *v, double *r,
+                         double *part, BcgsState *st, const GmPatchSrc *ps = nullptr);
+hipError_t launch_bcgs_t(cdfem_ctx *c, const double *w, const double *dinv, double *x, const double *p, double *r,
+                         double *t, const double *rh, double *part, BcgsState *st, BcgsState *poll,
+                         const GmPatchSrc *ps = nullptr);
 hipError_t launch_stream(cdfem_ctx *c, int mode, const double *a, double *b, int64_t n);
 // ILU(0) (ilu_kernels.hip): factor + capture once per operator; apply: ilu.z = (LU)^{-1} d_w[4]
 void ilu_setup(cdfem_ctx *c);

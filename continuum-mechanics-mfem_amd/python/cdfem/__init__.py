@@ -10,7 +10,7 @@ The classes mirror the reference's operator interface on the hot path
     ParBilinearForm-like  -> Context.pa_setup(...)   (Diffusion/Convection/Mass integrators + Assemble)
     Operator::Mult        -> Context.mult(x)          (constrained=True: the FormLinearSystem operator)
     FormLinearSystem      -> Context.form_linear_system(x, b)
-    Krylov Mult(B, X)     -> Context.solve(B, method="cg"|"gmres", ...)
+    Krylov Mult(B, X)     -> Context.solve(B, method="cg"|"gmres"|"bicgstab", ...)
 """
 from __future__ import annotations
 
@@ -26,13 +26,22 @@ HEADER_PATH = os.path.abspath(os.path.join(_PKG_ROOT, "..", "include", "cdfem.h"
 
 DIFFUSION, CONVECTION, MASS = 1, 2, 4
 HOST, DEVICE = 0, 1
-CG, GMRES = 0, 1
+CG, GMRES, BICGSTAB = 0, 1, 2
+METHODS = {"cg": CG, "gmres": GMRES, "bicgstab": BICGSTAB, "bcgs": BICGSTAB}
 PC_NONE, PC_JACOBI, PC_ILU = 0, 1, 2
 _PCS = {"none": PC_NONE, "jacobi": PC_JACOBI, "ilu": PC_ILU}
 RULE_OPERATOR, RULE_LINEARFORM, RULE_ERROR, RULE_DIFFUSION, RULE_CONVECTION, RULE_MASS = 0, 1, 2, 3, 4, 5
 K_APPLY, K_E2L, K_UPDATE, K_DIRECTION, K_ORTH = 0, 1, 2, 3, 4
 
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_NOT_CONVERGED, ERR_COMM = range(7)
+
+
+def method_id(name):
+    """Solver id of a method name ("bcgs", PETSc's spelling, is "bicgstab"); an unknown name is an error."""
+    try:
+        return METHODS[name]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown Krylov method {name!r}: one of {sorted(METHODS)}") from None
 
 
 class CdfemError(RuntimeError):
@@ -549,7 +558,7 @@ class Context:
 
     def solve(self, B, method="cg", pc="jacobi", rel_tol=1e-12, abs_tol=0.0, max_iter=500, restart=30,
               check_every=16, raise_on_fail=False):
-        prm = SolverParams(CG if method == "cg" else GMRES, _PCS[pc],
+        prm = SolverParams(method_id(method), _PCS[pc],
                            int(max_iter), int(restart), float(rel_tol), float(abs_tol), int(check_every), 0)
         res = SolverResult()
         B = _f64(B)
@@ -715,7 +724,7 @@ class Context:
 
     def solve_device(self, dB, dX, method="cg", pc="jacobi", rel_tol=0.0, abs_tol=0.0, max_iter=100,
                      restart=30, check_every=0):
-        prm = SolverParams(CG if method == "cg" else GMRES, _PCS[pc],
+        prm = SolverParams(method_id(method), _PCS[pc],
                            int(max_iter), int(restart), float(rel_tol), float(abs_tol),
                            int(check_every if check_every else max_iter), 0)
         res = SolverResult()

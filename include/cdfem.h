@@ -49,7 +49,7 @@ enum { CDFEM_DIFFUSION = 1, CDFEM_CONVECTION = 2, CDFEM_MASS = 4 };
 /* pointer locations */
 enum { CDFEM_HOST = 0, CDFEM_DEVICE = 1 };
 /* Krylov methods and preconditioners */
-enum { CDFEM_CG = 0, CDFEM_GMRES = 1 };
+enum { CDFEM_CG = 0, CDFEM_GMRES = 1, CDFEM_BICGSTAB = 2 };
 enum { CDFEM_PC_NONE = 0, CDFEM_PC_JACOBI = 1, CDFEM_PC_ILU = 2 };
 /* quadrature rules whose points the host may need for coefficient evaluation.  Quads / hexes: one
  * operator rule (Gauss n = p + 2, shared by the three integrators; DIFFUSION / CONVECTION / MASS
@@ -191,10 +191,23 @@ int cdfem_form_linear_system(cdfem_ctx *ctx, const double *x, const double *b, d
  * estimate (PETSc rnorm).  CDFEM_PC_ILU = ILU(0), natural ordering, no shift: PETSc
  * "-pc_type bjacobi -sub_pc_type ilu" on one rank (Input/petsc_circle.opts:6-8); GMRES on assembled
  * (cdfem_fa_setup) operators, single rank.  Multi-rank slabs: CG and GMRES with none / Jacobi.
+ * BiCGStab (CDFEM_BICGSTAB) follows PETSc KSPBCGS with left preconditioning (none, Jacobi, or ILU(0)
+ * under GMRES's conditions) and a zero initial guess; restart is ignored.  With r = rh = M^{-1} B,
+ * res0 = ||r||, ttol = max(rtol res0, atol), rho_old = alpha = omega_old = 1, p = v = 0, iteration i is
+ *   rho = (r, rh); beta = (rho / rho_old)(alpha / omega_old); p = r + beta (p - omega_old v);
+ *   v = M^{-1} A p; alpha = rho / (v, rh); s = r - alpha v; t = M^{-1} A s; omega = (s, t) / (t, t);
+ *   x += alpha p + omega s; r = s - omega t; converged when ||r|| <= ttol
+ * (t = 0: x += alpha p, converged if s = 0).  iterations = these iterations, two operator applies
+ * each; initial_norm = res0; final_norm = the last ||r||.  rho = 0, (v, rh) = 0 or t = 0 with s != 0 is
+ * a breakdown (PETSc KSP_DIVERGED_BREAKDOWN): CDFEM_ERR_NOT_CONVERGED, converged = 0, and
+ * cdfem_last_error names it.  Multi-rank: none / Jacobi on slabs, ILU(0) on a general partition.
+ * After a BiCGStab solve cdfem_kernel_bytes(CDFEM_K_UPDATE) is the traffic of one iteration's five
+ * vector kernels and cdfem_kernel_name(CDFEM_K_UPDATE) is "k_bcgs_v<S=0>" (they read the Mult's output
+ * vector) or "k_bcgs_v<S=4p+1>" (they read the structured Mult's patch buffer, "gm_pb").
  * Returns CDFEM_ERR_NOT_CONVERGED (result filled) when max_iter is reached.                     */
 typedef struct {
-    int method;        /* CDFEM_CG / CDFEM_GMRES */
-    int pc;            /* CDFEM_PC_NONE / CDFEM_PC_JACOBI / CDFEM_PC_ILU (GMRES on FA operators) */
+    int method;        /* CDFEM_CG / CDFEM_GMRES / CDFEM_BICGSTAB */
+    int pc;            /* CDFEM_PC_NONE / CDFEM_PC_JACOBI / CDFEM_PC_ILU (GMRES, BiCGStab on FA operators) */
     int max_iter;
     int restart;       /* GMRES restart (PETSc default 30) */
     double rel_tol;
@@ -443,9 +456,10 @@ int cdfem_fp64_bench(cdfem_ctx *ctx, int mode, int reps, double *tflops);
  * "spmv_xcd": 1 (default) — contiguous slice range per XCD for the windowed SpMV layout.
  * "gm_ept": 0 (default, auto) — entries per thread of the GMRES orthogonalisation passes (4, 5, 6
  *           or 8); auto takes the smallest whose grid is resident in one round (same results).
- * "gm_pb": 1 (default) — GMRES on the structured patch-buffer Mult (one rank, Jacobi or no
- *          preconditioner): the first orthogonalisation pass sums each row's patch entries itself, so
- *          the Mult's row-sum kernel and its output vector's write and re-read go away (same sums in
+ * "gm_pb": 1 (default) — GMRES and BiCGStab on the structured patch-buffer Mult (one rank, Jacobi
+ *          or no preconditioner): the kernel that takes the Mult's result (GMRES's first
+ *          orthogonalisation pass, BiCGStab's k_bcgs_v / k_bcgs_t) sums each row's patch entries itself,
+ *          so the Mult's row-sum kernel and its output vector's write and re-read go away (same sums in
  *          the same order: bitwise the same iterates); 0 = the Mult's own row sums.
  * Variants measured slower and removed in round 3 (their records stay under profiles/r02_ab_*):
  * brick element cores 1-10 and the four-waves-per-brick kernel, x-fold / paired x updates, the
