@@ -354,8 +354,11 @@ static BrickGeom geom_of(const cdfem_ctx *c)
         const int n = (uniform_elem(c) && c->p == 2) ? 2 : 4;
         stag = (c->ncu > 0 && (1 << sh) == c->ncu) ? (sh | (n << 4)) : 0;
     }
+    // the uniform-box apply built for 4 waves per SIMD (CDFEM_BUM_ONE_ROUND, brick_um.hip um_waves: the class
+    // table) holds 16 workgroups per CU at once, the others 8 to 12
+    const bool one_round = kUmOneRound && uniform_diag(c) && c->p == 2;
     return BrickGeom{c->nbx, c->nby, c->nbz, (int)c->Lx, (int)c->Ly, (int)c->Lz, c->brick_xcd, 0, 1, c->d_bess,
-                     stag, 8 * c->ncu};
+                     stag, (one_round ? 16 : 8) * c->ncu, 16 * c->ncu};
 }
 
 int brick_count(const cdfem_ctx *c) { return c->p >= 3 ? c->hb_nblk : c->nblk; }
@@ -758,6 +761,9 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv,
 // napart) in one fixed order and takes MFEM's den step itself (workgroup 0 records it), so the
 // one-block den finalizer and its launch go away; the grid is a few hundred to a few thousand
 // workgroups (grid-stride loop) to keep the redundant sums small, and its partials go to part.
+// bsum (DS; set_option "cg_beta_sum", one rank before the uniform-box apply): after its partial, each workgroup
+// counts its arrival on one agent-scope counter, and the last one sums the partials once for the next apply
+// (the kernel's tail); nullptr: the apply sums the vector itself.
 // UD (pa_uniform_diag, a uniform p = 2 box): dinv is the 64-entry class table of the Jacobi scale, held in
 // LDS; a dof takes 1 if essential, else the entry of its lattice class (udiag_class per axis).  Both loops
 // take it, so that the apply and the update use the same scale whatever brick_upd_pb says.
@@ -769,11 +775,12 @@ k_cg_update_faces(double *__restrict__ x, double *__restrict__ r, const double *
                   const FastDiv fdx, const FastDiv fdxy, int zlo_shared,
                   const double *__restrict__ remote_lo, const double *__restrict__ remote_hi,
                   double *__restrict__ part, KrylovState *__restrict__ st, int den_step,
-                  const double *__restrict__ apart, int napart)
+                  const double *__restrict__ apart, int napart, double *__restrict__ bsum)
 {
     constexpr int s1 = S - 1, sz1 = SZ - 1;
     constexpr uint32_t PV = (uint32_t)S * S * SZ;  // patch entries per brick / block
     __shared__ double sh[kRedThreads / 64 + 1];
+    __shared__ int s_last;  // DS, cg_beta_sum: this workgroup arrived last
     __shared__ double s_tab[UD ? kUdiagN : 1];
     static_assert(!UD || kRedThreads >= kUdiagN, "UD: one table entry per thread");
     if (st->done) return;
@@ -897,6 +904,40 @@ k_cg_update_faces(double *__restrict__ x, double *__restrict__ r, const double *
     }
     const double bs = block_sum(acc, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = bs;
+    if constexpr (DS) {
+        // cg_beta_sum: the betanom sum taken once.  Thread 0 counts the workgroup's arrival with an agent-scope
+        // release (its partial above is then visible to whoever reads the count); the workgroup whose add
+        // returns the last count takes an agent-scope acquire and sums the partials in the betanom-fold apply's
+        // own order (lane t adds partials t, t + 64, ... in increasing order from 0.0, then wave_sum), so the
+        // value is bitwise what every apply workgroup would form from the vector.  It resets the counter for
+        // the next launch.  Nobody waits: the kernel boundary hands the sum to the apply.  Every return above
+        // (st->done, den == 0) is taken by all workgroups of a launch or by none (done is set between launches
+        // only, den is the same sum everywhere), so a launch counts gridDim.x arrivals or none.
+        // Off by default: the release writes this XCD's L2 back in each of C2's 1,024 workgroups, which all end
+        // together, and costs the update more than the apply gains (profiles/r14/ab_c2_one_round/).
+        if (bsum == nullptr) return;
+        uint32_t *const bcnt = reinterpret_cast<uint32_t *>(bsum + 1);
+        if (threadIdx.x == 0)
+            s_last = __hip_atomic_fetch_add(bcnt, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+        __syncthreads();
+        if (!s_last || threadIdx.x >= 64) return;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        constexpr int NPL = 16;  // (gridDim.x <= 64 NPL: cg_folds_fit)
+        double pv[NPL];
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) {
+            const unsigned k = threadIdx.x + 64u * i;
+            pv[i] = k < gridDim.x ? __hip_atomic_load(&part[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+        }
+        double v = 0.0;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) v += pv[i];
+        v = wave_sum(v);
+        if (threadIdx.x == 0) {
+            *bsum = v;
+            __hip_atomic_store(bcnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 
 
@@ -1324,6 +1365,15 @@ bool cg_beta_fold_ok(const cdfem_ctx *c)
     return cg_folds_fit(c) && (!multi_rank(c) || cg_mr_fold(c));
 }
 
+// the betanom sum taken once by the update's last workgroup (set_option "cg_beta_sum"): one rank, both folds
+// on, and the consumer is the uniform-box apply (brick_um.hip), which then loads one double; the Kronecker-form
+// apply and the multi-rank fold (which all-reduces the partials first) read the vector
+bool cg_beta_sum_on(const cdfem_ctx *c)
+{
+    return c->cg_beta_sum != 0 && c->d_bsum != nullptr && !multi_rank(c) && cg_beta_fold_ok(c) && cg_den_fold_on(c) &&
+           uniform_elem(c) && c->p == 2;
+}
+
 // den step inside the update (p <= 2: every update workgroup sums the apply's partials, one per
 // 64-element brick; the high-order blocks leave too many partials and keep the finalizer)
 bool cg_den_fold_on(const cdfem_ctx *c)
@@ -1373,6 +1423,9 @@ hipError_t launch_cg_update_faces(cdfem_ctx *c, double *x, double *r, const doub
     // with it the swap of dinv for the table is right for the kernel that runs
     const bool ud = uniform_diag(c) && dinv == c->d_dinv && c->p == 2;
     if (ud) dinv = c->d_udiag;
+    // cg_beta_sum: the last workgroup sums the betanom partials for the uniform-box apply (one double, then
+    // the arrival counter)
+    double *const bsum = ds && cg_beta_sum_on(c) ? c->d_bsum : nullptr;
     // the patch: edge * p + 1 points a side, bricks of 4 elements at p <= 2, blocks of 2 x 2 x ho_block_z at
     // p = 3, 4 (keyed 10 p + ho_block_z; p = 4 on 2^3 blocks shares the 9^3 patch with p = 2)
     const int pez = c->p <= 2 ? c->p : 10 * c->p + c->hb_ez;
@@ -1386,7 +1439,7 @@ hipError_t launch_cg_update_faces(cdfem_ctx *c, double *x, double *r, const doub
                 hipLaunchKernelGGL((k_cg_update_faces<S, XF(), PB(), DS(), EP(), SZ, UD()>), dim3(ugrid),
                                    dim3(kRedThreads), 0, c->stream, x, r, d, dinv, c->d_face, c->d_ess, g, fdx, fdxy,
                                    c->zlo_shared, remote_lo, remote_hi, upart, c->d_state, (int)den_step, apart,
-                                   napart);
+                                   napart, bsum);
                 return hipGetLastError();
             }
         });

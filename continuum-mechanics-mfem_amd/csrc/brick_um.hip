@@ -84,8 +84,12 @@ constexpr bool um_group_padded() { return kUmRow[4 * G + 1] < 0 || kUmRow[4 * G 
 // with its rows in kUmRow's: [mt][ks][lane] = A_e[kUmRow[16 mt + (lane & 15)]][4 ks + (lane >> 4)], 0 in
 // the padding, 14 doubles per lane held for the whole kernel.  B (lane: input dof 4 ks + (lane >> 4) of
 // element 16 nt + (lane & 15)) comes straight from the LDS patch, 0 for an element of a partial brick
-// outside the box (its column of Y and its den terms are then exactly 0).  The den terms and the E->L
-// sum are taken in the accumulator layout (kUmRow above); LDS is the input and the output patch.
+// outside the box (its column of Y is then exactly 0).  The E->L sum is taken in the accumulator layout
+// (kUmRow above).  LDS is one patch: the input until the last B operand is read, then zeroed and the output.
+// den is taken from the assembled patch in the final store loop: sum over (element, dof) of X Y = sum over
+// patch positions of in[pos] * out[pos], because every element sharing a position reads the same in[pos]
+// (0 on essential and out-of-lattice positions) and a masked element has Y = 0; the lane that formed a
+// position's d stores its output, so in[pos] is still at hand (dev[], s_dev) and den is one FMA per position.
 // The k order (columns of A_e, B rows) is the dofs' own: consecutive dofs lie an odd number of doubles
 // apart (1, 7 or 61), so the two dofs of a 32-lane half already miss each other's banks and the reads
 // sit on the 2-way floor of the 16 element origins (2 ex + 18 ey doubles: 12 distinct bank pairs).
@@ -97,9 +101,27 @@ constexpr bool um_group_padded() { return kUmRow[4 * G + 1] < 0 || kUmRow[4 * G 
 // the first brick, 3 at the last lattice plane where the patch holds it.  The gather packs a position's
 // table offset into 9 bits, three positions per register.  Positions past the lattice read some finite
 // entry and keep d = 0 (r and d_old load 0 there).
+// BF: 0 no betanom fold, 1 the fold from the update's partial vector (every workgroup sums it: several
+// ranks, and cg_beta_sum 0), 2 from the one sum the update's last workgroup left (cg_beta_sum: one load).
+// Residency: the time is memory latency covered by resident waves.  C2 launches 4,096 single-wave
+// workgroups on 256 CUs, 16 per CU; at 3 waves per SIMD 12 are resident, so every CU runs a full round and
+// then a round of 4.  At 4 waves per SIMD (<= 128 registers, <= 10,240 B of LDS) all 16 are resident at once.
+// CDFEM_BUM_ONE_ROUND 1 builds that: um_waves names the instantiations that reach 128 registers without
+// scratch (the table forms, those of a partial box's first apply excepted), which then park part of dev[] in
+// LDS and, with the partial vector (BF 1), sum it before the gather is issued instead of under it (um_early:
+// one more dependent round trip per wave, and the partials' 32 registers are free when the gather's loads go
+// out).  Measured: the fourth wave does not pay by the project's rule (profiles/r14/ab_c2_one_round/), so
+// the default build keeps the bound of 2 and its 3 waves.  No instantiation of either build uses scratch
+// (tests/test_resource_usage.py).
 // ================================================================================================
-template <bool XF, bool BF, bool FULL, bool UD>
-__global__ void __launch_bounds__(64, 2)
+constexpr bool um_early(int BF, bool UD) { return kUmOneRound && BF == 1 && UD; }
+constexpr int um_waves(bool XF, int BF, bool FULL, bool UD)
+{
+    return kUmOneRound && UD && !(BF != 0 && !XF && !FULL) ? 4 : 2;
+}
+
+template <bool XF, int BF, bool FULL, bool UD>
+__global__ void __launch_bounds__(64, um_waves(XF, BF, FULL, UD))
 k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const double *__restrict__ d_old,
            double *__restrict__ d_new, double *__restrict__ face, const double *__restrict__ amat,
            const uint8_t *__restrict__ ess, const BrickGeom g, int zlo_shared, double *__restrict__ part,
@@ -108,20 +130,28 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
 {
     constexpr int P = 2, S = kBrick * P + 1, S2 = S * S, S3 = S * S * S, NDE = kUmN;
     static_assert(S == 9, "um_slot_off is written for the 9^3 patch");
-    __shared__ double s_in[S3];
-    __shared__ double s_out[S3];
+    __shared__ double s_pat[S3];  // the input patch, then (zeroed after the last B operand is read) the output patch
     __shared__ double s_tab[UD ? kUdiagN + 1 : 1];  // the class table, then 1 (what an essential dof takes)
+    // 4 waves: the d of a lane's first NST positions wait in LDS for the store loop (slot [k][lane], read back
+    // by the lane that wrote it), the rest in registers: 14 registers less across the MFMA block, where the 64
+    // accumulator and 28 A registers are live, and LDS stays within a sixteenth of a CU's (9,944 B)
+    constexpr int NST = um_waves(XF, BF, FULL, UD) >= 4 ? 7 : 0;
+    __shared__ double s_dev[NST ? NST * 64 : 1];
     if (st->done) return;
     brick_stagger(g);
     double beta = st->beta;
-    constexpr int NPL = 16;  // BF: partials per lane (nupart <= 64 NPL)
-    double pv[NPL];
-    if constexpr (BF) {
+    constexpr int NPL = 16;  // BF 1: partials per lane (nupart <= 64 NPL)
+    double pv[BF == 1 ? NPL : 1];
+    if constexpr (BF == 1) {
         if (kk > 0) {  // (buffer loads: past nupart they read 0, no branch per load)
             const auto bu = brsrc(upart, 8u * (uint32_t)nupart);
 #pragma unroll
             for (int i = 0; i < NPL; ++i) pv[i] = bload(bu, 8u * ((uint32_t)threadIdx.x + 64u * i));
         }
+    } else if constexpr (BF == 2) {
+        // (the update's last workgroup summed its partials in the order below: one load, written before this
+        // launch began)
+        if (kk > 0) pv[0] = upart[0];
     }
     const double alpha_prev = XF ? st->alpha : 0.0;
     const int t = threadIdx.x;
@@ -157,7 +187,7 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
     uint32_t woffv[NI];
     uint32_t dbits = 0, ebits = 0;
     uint8_t ev[NI];
-    double dev[NI];  // the essential entries' d (each position is formed and stored by the same thread)
+    double dev[NI];  // the positions' d (each position is formed and stored by the same thread)
     const uint32_t uLx = (uint32_t)Lx, uLxy = (uint32_t)Lxy;
     constexpr uint32_t wdx = 64 % S, wdy = (64 / S) % S, wdz = 64 / (S * S);
     const uint32_t dgid = wdx + wdy * uLx + wdz * uLxy, cxd = uLx - S, cyd = uLxy - S * uLx;
@@ -205,19 +235,20 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
         const double dn = m * rv[k] + beta * ov[k];  // 0 outside the lattice
         bstore(bd, woffv[k], dn);
         if constexpr (XF) bstore(bxf, woffv[k], xv[k] + alpha_prev * ov[k]);
-        den += (e && ((dbits >> k) & 1u)) ? dn * dn : 0.0;  // (A_c d)_i = d_i on ess dofs
-        s_in[i] = e ? 0.0 : dn;
-        s_out[i] = 0.0;
+        s_pat[i] = e ? 0.0 : dn;
         ebits |= (uint32_t)e << k;
-        dev[k] = ((dbits >> k) & 1u) ? dn : 0.0;
+        if constexpr (k < NST) s_dev[64 * k + t] = dn;
+        else dev[k] = dn;
     };
-    static_for<0, NI>(gather);
-    if constexpr (BF) {
+    auto beta_fold = [&]() -> bool {  // the betanom step of the previous update; true: the solve stops here
         if (kk > 0) {
-            double v = 0.0;
+            double B = pv[0];
+            if constexpr (BF == 1) {
+                double v = 0.0;
 #pragma unroll
-            for (int q = 0; q < NPL; ++q) v += pv[q];
-            const double B = wave_sum(v);
+                for (int q = 0; q < NPL; ++q) v += pv[q];
+                B = wave_sum(v);
+            }
             // cg_update_logic's decision (cg_stop_kind), taken identically by every workgroup at the
             // host's update count kk; workgroup 0 records it at the same kk
             const bool stop = cg_stop_kind(st, B, kk) != kCgGoOn;
@@ -227,9 +258,18 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
 #endif
                 cg_update_logic_at(st, B, kk);
             }
-            if (stop) return;
+            if (stop) return true;
             beta = B / st->nom;
         }
+        return false;
+    };
+    constexpr bool EARLY = um_early(BF, UD);
+    if constexpr (BF != 0 && EARLY) {
+        if (beta_fold()) return;
+    }
+    static_for<0, NI>(gather);
+    if constexpr (BF != 0 && !EARLY) {
+        if (beta_fold()) return;
     }
     if constexpr (UD) {
         s_tab[t] = mv[0];
@@ -263,37 +303,38 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
                 const bool ok = j < NDE && vxy && (FULL || gz0 + P * nt + P < g.Lz);
-                const double xin = s_in[P * nt * S2 + ob0 + jo];
+                const double xin = s_pat[P * nt * S2 + ob0 + jo];
                 const double bv = ok ? xin : 0.0;
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt)
                     acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mt][ks], bv, acc[mt][nt], 0, 0, 0);
             }
         }
-        // den: sum over (dof, element) of X Y, and the E->L sum, both in the accumulator layout: group
-        // G = 4 mt + i, this lane's dof of it at patch offset so (-1: a padding slot, whose Y is 0)
+        // every B operand is read: the patch is zeroed (each lane its own positions) and takes the output
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < NI; ++k)
+            if (k < NI - 1 || t + 64 * k < S3) s_pat[t + 64 * k] = 0.0;
+        __syncthreads();
+        // the E->L sum in the accumulator layout: group G = 4 mt + i, this lane's dof of it at patch offset so
+        // (-1: a padding slot, whose Y is 0)
         static_for<0, 8>([&](auto gc) {
             constexpr int G = decltype(gc)::value, mt = G / 4, i = G % 4;
             constexpr bool PADG = um_group_padded<G>();
             const int so = um_slot_off<G>(kg);
             const bool live = !PADG || so >= 0;
             const int o = ob0 + (PADG ? max(so, 0) : so);
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                const double xin = s_in[P * nt * S2 + o];
-                den += live ? xin * acc[mt][nt][i] : 0.0;
-            }
             if (live) {
 #if CDFEM_BUM_ADD == 1
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt)
-                    (void)__hip_atomic_fetch_add(&s_out[P * nt * S2 + o], acc[mt][nt][i], __ATOMIC_RELAXED,
+                    (void)__hip_atomic_fetch_add(&s_pat[P * nt * S2 + o], acc[mt][nt][i], __ATOMIC_RELAXED,
                                                  __HIP_MEMORY_SCOPE_WORKGROUP);
 #else
                 // layers nt and nt + 2 share no position (z = 2 nt + dz): two reads in flight per batch
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    double *const p0 = &s_out[P * h * S2 + o], *const p1 = &s_out[P * (h + 2) * S2 + o];
+                    double *const p0 = &s_pat[P * h * S2 + o], *const p1 = &s_pat[P * (h + 2) * S2 + o];
                     const double v0 = *p0, v1 = *p1;
                     *p0 = v0 + acc[mt][h][i];
                     *p1 = v1 + acc[mt][h + 2][i];
@@ -316,8 +357,15 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
         for (int k = 0; k < NI; ++k) {
             const unsigned i = to + 64 * k;
             if (k == NI - 1 && i >= S3) break;
-            double v = s_out[i];
-            v = ((ebits >> k) & 1u) ? dev[k] : v;
+            // an essential row's entry is (A_c d)_i = d_i from its writer (where it counts in den), 0 from the
+            // other bricks; den = sum over positions of d~ y (d~ = 0 on essential rows: every element sharing
+            // a position read the same d~, and masked elements have y = 0) + the writers' d^2 on essential rows:
+            // with the entry formed first, both are d times the entry
+            double v = s_pat[i];
+            const double dk = k < NST ? s_dev[64 * k + to] : dev[k];
+            const double dw = ((dbits >> k) & 1u) ? dk : 0.0;
+            v = ((ebits >> k) & 1u) ? dw : v;
+            den += dk * v;
             bstore(bp, 8u * (base + (uint32_t)pw.z * A + (uint32_t)pw.y * R + (uint32_t)pw.x), v);
             pw.next();
         }
@@ -358,11 +406,17 @@ hipError_t launch_brick_um(cdfem_ctx *c, const BrickGeom &g, unsigned nbrick_lau
     // the Jacobi scale from the class table (not under pc = none, whose dinv is the ones vector)
     const bool ud = uniform_diag(c) && dinv == c->d_dinv;
     if (ud) dinv = c->d_udiag;
-    dispatch_bools(x != nullptr, kk >= 0, full, ud, [&](auto XF, auto BF, auto FU, auto UD) {
-        const auto kern = k_brick_cg<XF(), BF(), FU(), UD()>;
-        CDFEM_LAUNCH_ON(c, whole, s, kern, grid, block, 0, r, dinv, d_old, d_new, c->d_face, c->d_uelem, c->d_ess, g,
-                        c->zlo_shared, dpart, c->d_state, x, upart, nupart, kk, c->d_gsum, c->d_gcnt, c->den_grp,
-                        c->nblk);
+    // the betanom fold: 1 from the update's partials, 2 from their one sum (cg_beta_sum)
+    const bool bs = kk >= 0 && cg_beta_sum_on(c);
+    if (bs) upart = c->d_bsum;
+    dispatch_value<0, 1, 2>(kk < 0 ? 0 : bs ? 2 : 1, 0, [&](auto BF) {
+        dispatch_bools(x != nullptr, full, ud, [&](auto XF, auto FU, auto UD) {
+            const auto kern = k_brick_cg<XF(), BF(), FU(), UD()>;
+            CDFEM_LAUNCH_ON(c, whole, s, kern, grid, block, 0, r, dinv, d_old, d_new, c->d_face, c->d_uelem, c->d_ess,
+                            g, c->zlo_shared, dpart, c->d_state, x, upart, nupart, kk, c->d_gsum, c->d_gcnt, c->den_grp,
+                            c->nblk);
+        });
+        return 0;
     });
     return hipGetLastError();
 }

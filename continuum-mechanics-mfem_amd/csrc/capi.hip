@@ -178,6 +178,7 @@ void free_mesh(cdfem_ctx *c)
     dfree(c->d_small);
     dfree(c->d_gsum);
     dfree(c->d_gcnt);
+    dfree(c->d_bsum);
     c->gsum_cap = 0;
     c->den_grp = 1;
     dfree(c->d_hbpart);
@@ -538,6 +539,11 @@ void solve_cg_brick(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB
         c->gsum_cap = ndp;
     }
     c->den_grp = grp;
+    // cg_beta_sum: the betanom sum and the update's arrival counter (zeroed once: the last arriver resets it)
+    if (!mr && bfold && !c->d_bsum) {
+        c->d_bsum = dalloc<double>(2);
+        HIPCHK(hipMemsetAsync(c->d_bsum, 0, 2 * sizeof(double), c->stream));
+    }
     double *const dparts = grp > 1 ? c->d_gsum : c->d_part;  // what the mr fold all-reduces (ndp of them)
     int nupd = 0;
     int napply = 0;
@@ -2094,6 +2100,9 @@ int cdfem_set_option(cdfem_ctx *c, const char *key, int value)
         } else if (k == "cg_beta_fold") {
             if (value != 0 && value != 1) throw ArgError("cg_beta_fold must be 0 or 1");
             c->cg_beta_fold = value;
+        } else if (k == "cg_beta_sum") {
+            if (value != 0 && value != 1) throw ArgError("cg_beta_sum must be 0 or 1");
+            c->cg_beta_sum = value;
         } else if (k == "cg_den_fold") {
             if (value != 0 && (value < 64 || value > 16384)) throw ArgError("cg_den_fold must be 0 or 64..16384");
             c->cg_den_fold = value;

@@ -285,6 +285,10 @@ struct cdfem_ctx {
     hipEvent_t ov_ev[2] = {};           // fork / join of the side stream
     int brick_mult_pb = 1;              // set_option "brick_mult_pb": structured Mult through the patch buffer
     int cg_beta_fold = 1;               // set_option "cg_beta_fold": brick CG betanom step in the next apply
+    int cg_beta_sum = 0;                // set_option "cg_beta_sum": with it, on one rank before the uniform-box apply, the
+                                        // update's last workgroup sums the betanom partials once (cg_beta_sum_on);
+                                        // off: measured slower (profiles/r14/ab_c2_one_round/)
+    double *d_bsum = nullptr;           // [2] that sum, then the update's arrival counter (0 between launches)
     int cg_mr_fold = 1;                 // set_option "cg_mr_fold": both folds on several ranks (partials all-reduced)
     double *d_small = nullptr;          // a few doubles of device scratch (mr_fold_agreed's all-reduce)
     int cg_den_fold = 1024;             // set_option "cg_den_fold": brick CG den step in the update (N workgroups; 0 off)
@@ -519,6 +523,7 @@ hipError_t launch_brick_cg2(cdfem_ctx *c, const double *r, const double *dinv, c
                             double *d_new, double *q, double *x = nullptr, int bfkk = -1);
 int cg_den_fold_grid(const cdfem_ctx *c);
 bool cg_beta_fold_ok(const cdfem_ctx *c);
+bool cg_beta_sum_on(const cdfem_ctx *c);
 // x-fold CG after the loop: x += alpha d_m when the last update's x term is still pending
 // (d_m in dbuf[(m - 1) & 1], m = the final iteration)
 hipError_t launch_cg_xflush(cdfem_ctx *c, double *x, const double *d0, const double *d1);

@@ -262,6 +262,12 @@ int cdfem_fp64_bench(cdfem_ctx *ctx, int mode, int reps, double *tflops);
  *              every workgroup sums the update's partials with its patch gather in flight, and the
  *              one-block update finalizer is not launched (iterates agree with 0 to rounding; C2:
  *              60.8 against 62.6 us per iteration, profiles/r04/ab_c2_beta_fold.json).
+ * "cg_beta_sum": 0 (default) — 1: with cg_beta_fold on one rank, before the uniform-box apply (pa_uniform), the
+ *              update's last-arriving workgroup (an agent-scope arrival count with release / acquire, no
+ *              waiting) sums the betanom partials once, in the order every apply workgroup would, and the apply
+ *              loads that one double (bitwise the same iterates).  Off: the release in each of C2's 1,024
+ *              update workgroups costs 23 us per iteration (profiles/r14/ab_c2_one_round/).  The Kronecker-form
+ *              apply and several ranks always read the vector.
  * "cg_den_fold": 1024 (default) — N (64..16384): the one-rank brick CG takes MFEM's den step inside
  *              the update kernel, run as N workgroups that each sum the apply's den partials in one
  *              fixed order; the one-block den finalizer is not launched (iterates agree with the
