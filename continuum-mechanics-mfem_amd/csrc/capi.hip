@@ -1,91 +1,66 @@
-// capi.hip — the C-ABI of libcdfem.so (include/cdfem.h): context, mesh/space upload, partial
-// assembly, FormLinearSystem, Krylov solves, profiling.  Host-side orchestration only; all
-// arithmetic on the hot path runs in the HIP kernels of pa_kernels.hip / vec_kernels.hip.
+// capi.hip — the C-ABI of libcdfem.so (include/cdfem.h): context, mesh/space upload, partial and full
+// assembly setup, FormLinearSystem, the entry to the Krylov solves, profiling.  Host-side orchestration
+// only: the Krylov drivers are in solve.hip, the option table in options.hpp, the cost model in model.hip,
+// and all arithmetic on the hot path runs in the HIP kernels (pa_kernels.hip, vec_kernels.hip, ...).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <new>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "cdfem_internal.hpp"
+#include "host_util.hpp"
 #include "brick_core.hpp"
 
 using namespace cdfem;
 
-namespace {
-
-struct HipError : std::runtime_error {
-    explicit HipError(const std::string &m) : std::runtime_error(m) {}
-};
-struct ArgError : std::runtime_error {
-    explicit ArgError(const std::string &m) : std::runtime_error(m) {}
-};
-struct StateError : std::runtime_error {
-    explicit StateError(const std::string &m) : std::runtime_error(m) {}
-};
-struct UnsupportedError : std::runtime_error {
-    explicit UnsupportedError(const std::string &m) : std::runtime_error(m) {}
-};
-
-inline void hip_check(hipError_t e, const char *what)
+// ---- profiling helpers ---------------------------------------------------------------------------
+void cdfem::prof_mark(cdfem_ctx *c, int k, bool begin)
 {
-    if (e != hipSuccess) throw HipError(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(x) hip_check((x), #x)
-
-template <typename F>
-int guarded(cdfem_ctx *c, F &&f)
-{
-    if (!c) return CDFEM_ERR_ARG;
-    try {
-        c->err.clear();
-        return f();
-    } catch (const ArgError &e) {
-        c->err = e.what();
-        return CDFEM_ERR_ARG;
-    } catch (const StateError &e) {
-        c->err = e.what();
-        return CDFEM_ERR_STATE;
-    } catch (const UnsupportedError &e) {
-        c->err = e.what();
-        return CDFEM_ERR_UNSUPPORTED;
-    } catch (const HipError &e) {
-        c->err = e.what();
-        return CDFEM_ERR_HIP;
-    } catch (const std::bad_alloc &) {
-        c->err = "host allocation failed";
-        return CDFEM_ERR_HIP;
-    } catch (const std::exception &e) {
-        c->err = e.what();
-        return CDFEM_ERR_ARG;
+    if (!c->profile || !((c->prof_mask >> k) & 1u)) return;
+    ProfileSlot &s = c->prof[k];
+    const size_t need = (size_t)(s.used + 1) * 2;
+    while (s.ev.size() < need) {
+        hipEvent_t e;
+        HIPCHK(hipEventCreate(&e));
+        s.ev.push_back(e);
+    }
+    if (begin) {
+        // recorded now AND armed: a CDFEM_LAUNCH before the end mark re-records the pair tightly
+        // around its own dispatch; any other launch leaves the plain event interval
+        HIPCHK(hipEventRecord(s.ev[2 * s.used], c->stream));
+        c->ext_ev[0] = s.ev[2 * s.used];
+        c->ext_ev[1] = s.ev[2 * s.used + 1];
+    } else {
+        if (c->ext_ev[0]) HIPCHK(hipEventRecord(s.ev[2 * s.used + 1], c->stream));  // not consumed
+        c->ext_ev[0] = c->ext_ev[1] = nullptr;
+        s.used++;
     }
 }
 
-template <typename T>
-void dfree(T *&p)
+void cdfem::prof_collect(cdfem_ctx *c)
 {
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
+    if (!c->profile) return;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (auto &s : c->prof) {
+        for (int i = 0; i < s.used; ++i) {
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, s.ev[2 * i], s.ev[2 * i + 1]));
+            s.total_ms += ms;
+            s.count++;
+            s.each.push_back(ms);
+        }
+        s.used = 0;
+    }
 }
 
-template <typename T>
-T *dalloc(size_t n)
-{
-    void *p = nullptr;
-    if (n == 0) n = 1;
-    HIPCHK(hipMalloc(&p, n * sizeof(T)));
-    return static_cast<T *>(p);
-}
-
-int nq_of(const cdfem_ctx *c, const Rule1D &r) { return c->dim == 3 ? r.q1 * r.q1 * r.q1 : r.q1 * r.q1; }
+namespace {
 
 // every element a parallelepiped: each vertex v (lexicographic, bit k = axis k) equals
 // v0 + sum_k bit_k (v_{2^k} - v0) up to the rounding of those coordinates (32 ulp of the largest
@@ -142,19 +117,13 @@ void free_mesh(cdfem_ctx *c)
     dfree(c->d_uelem);
     dfree(c->d_udiag);
     dfree(c->d_hoelem);
-    c->d_sdel = nullptr;
-    c->d_swide = nullptr;
     c->sell_nnz_wide = 0;
     dfree(c->d_hptr); dfree(c->d_hidx); dfree(c->d_sloc);
-    c->d_hptr = c->d_hidx = nullptr;
-    c->d_sloc = nullptr;
     c->lds_rows = 0;
     c->lds_max = 0;
     c->sell_lpr = 1;
     dfree(c->d_rperm); dfree(c->d_pv[0]); dfree(c->d_pv[1]); dfree(c->d_dinv_p);
-    c->d_rperm = nullptr; c->d_pv[0] = c->d_pv[1] = nullptr; c->d_dinv_p = nullptr;
     dfree(c->d_svals_c);
-    c->d_svals_c = nullptr;
     dfree(c->d_lfq);
     c->lfq_cap = 0;
     ilu_free(c);
@@ -209,46 +178,6 @@ static void upload_brick_ess(cdfem_ctx *c, int E, int EZ, int nbx, int nby, int 
     HIPCHK(hipMemcpy(c->d_bess, has.data(), has.size(), hipMemcpyHostToDevice));
 }
 
-// ---- profiling helpers ---------------------------------------------------------------------------
-void prof_mark(cdfem_ctx *c, int k, bool begin)
-{
-    if (!c->profile || !((c->prof_mask >> k) & 1u)) return;
-    ProfileSlot &s = c->prof[k];
-    const size_t need = (size_t)(s.used + 1) * 2;
-    while (s.ev.size() < need) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        s.ev.push_back(e);
-    }
-    if (begin) {
-        // recorded now AND armed: a CDFEM_LAUNCH before the end mark re-records the pair tightly
-        // around its own dispatch; any other launch leaves the plain event interval
-        HIPCHK(hipEventRecord(s.ev[2 * s.used], c->stream));
-        c->ext_ev[0] = s.ev[2 * s.used];
-        c->ext_ev[1] = s.ev[2 * s.used + 1];
-    } else {
-        if (c->ext_ev[0]) HIPCHK(hipEventRecord(s.ev[2 * s.used + 1], c->stream));  // not consumed
-        c->ext_ev[0] = c->ext_ev[1] = nullptr;
-        s.used++;
-    }
-}
-
-void prof_collect(cdfem_ctx *c)
-{
-    if (!c->profile) return;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (auto &s : c->prof) {
-        for (int i = 0; i < s.used; ++i) {
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, s.ev[2 * i], s.ev[2 * i + 1]));
-            s.total_ms += ms;
-            s.count++;
-            s.each.push_back(ms);
-        }
-        s.used = 0;
-    }
-}
-
 // (Re)build the element-block layout for a permutation perm[blk*64 + lane] = element (-1 pad):
 // element map [blk][l][lane] (ess negative), E->L positions, and the device permutation.
 void build_layout(cdfem_ctx *c, const std::vector<int32_t> &perm)
@@ -297,29 +226,6 @@ void build_layout(cdfem_ctx *c, const std::vector<int32_t> &perm)
     HIPCHK(hipStreamSynchronize(c->stream));
 }
 
-bool use_brick(const cdfem_ctx *c) { return c->structured && brick_supported(c->dim, c->p) && brick_fits(c); }
-
-// the high-order brick CG (3D p = 3, 4, affine box with constant coefficients: the Kronecker tile core on
-// 2^3-element blocks, brick_kernels.hip k_hobrick_cg, then the brick update); on several ranks a z-slab
-// of 2^3 blocks (round 6: the plane pack and exchange of the p = 2 brick CG, rank-local den sums)
-bool use_hobrick_cg(const cdfem_ctx *c)
-{
-    return c->ho_brick != 0 && c->structured && c->qlay == 1 && c->hb_nblk > 0 && tile_kron(c) && tile_den_ok(c) &&
-           (!multi_rank(c) || (c->part_mode == 1 && c->hb_ez == kHoBrickEdge)) && !c->fa_ready && brick_fits(c);
-}
-bool use_brick_cg(const cdfem_ctx *c) { return use_brick(c) || use_hobrick_cg(c); }
-
-const double *ones_vector(cdfem_ctx *c)
-{
-    if (!c->d_ones) {
-        c->d_ones = dalloc<double>(c->nl);
-        std::vector<double> one(c->nl, 1.0);
-        HIPCHK(hipMemcpyAsync(c->d_ones, one.data(), c->nl * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return c->d_ones;
-}
-
 void require_mesh(cdfem_ctx *c)
 {
     if (!c->mesh_ready) throw StateError("cdfem_mesh_upload has not been called");
@@ -349,44 +255,6 @@ void require_partition(cdfem_ctx *c)
                      " ranks) but no partition declared: call cdfem_set_slab or cdfem_set_shared");
 }
 
-// operator apply into y (device pointers): Ye = A_e x, y = E->L(Ye) [+ constraint]
-void op_apply(cdfem_ctx *c, const double *x, double *y, bool constrained)
-{
-    if (c->fa_ready) {  // assembled CSR: A, or the eliminated matrix for the constrained operator
-        prof_mark(c, CDFEM_K_APPLY, true);
-        HIPCHK(launch_spmv(c, constrained, x, y));
-        prof_mark(c, CDFEM_K_APPLY, false);
-        return;
-    }
-    if (use_brick(c)) {
-        prof_mark(c, CDFEM_K_APPLY, true);
-        HIPCHK(launch_brick_mult(c, x, y, constrained, 1));
-        prof_mark(c, CDFEM_K_APPLY, false);
-        prof_mark(c, CDFEM_K_E2L, true);
-        HIPCHK(launch_brick_mult(c, x, y, constrained, 2));
-        prof_mark(c, CDFEM_K_E2L, false);
-        return;
-    }
-    prof_mark(c, CDFEM_K_APPLY, true);
-    HIPCHK(launch_apply(c, x, c->d_Ye, constrained));
-    prof_mark(c, CDFEM_K_APPLY, false);
-    prof_mark(c, CDFEM_K_E2L, true);
-    HIPCHK(launch_e2l(c, c->d_Ye, x, y, constrained, 0));
-    prof_mark(c, CDFEM_K_E2L, false);
-}
-
-// the operator on the global (all-rank) space, rank-local L-vectors: the local apply, then the
-// shared planes summed with the neighbours (MFEM P^T A P on the true dofs, then P), and for the
-// constrained operator the essential rows reset to the identity (an essential dof on a shared
-// plane was set by both ranks, so the sum doubled it)
-void op_apply_global(cdfem_ctx *c, const double *x, double *y, bool constrained)
-{
-    op_apply(c, x, y, constrained);
-    if (!multi_rank(c)) return;
-    interface_sum(c, y);
-    if (constrained) HIPCHK(launch_set_ess(c, y, x));
-}
-
 // copy-in helper: returns a device pointer holding n doubles of src (staging when on host)
 const double *dev_in(cdfem_ctx *c, const double *src, int where, double *staging, size_t n)
 {
@@ -406,591 +274,8 @@ void dev_out(cdfem_ctx *c, double *dst, int where, const double *dsrc, size_t n)
     HIPCHK(hipStreamSynchronize(c->stream));
 }
 
-void ensure_dinv(cdfem_ctx *c)
-{
-    if (c->dinv_ready) return;
-    double *diag = c->d_w[7];
-    if (c->fa_ready) {
-        HIPCHK(launch_csr_diag(c, diag));
-    } else {
-        HIPCHK(launch_diag_elem(c, c->d_Ye));
-        HIPCHK(launch_e2l(c, c->d_Ye, nullptr, diag, false, 0));
-    }
-    interface_sum(c, diag);  // shared planes: the full diagonal (both ranks' elements)
-    HIPCHK(launch_dinv(c, diag, c->d_dinv));
-    // pa_uniform_diag: the class table of a uniform p = 2 box, checked against the vector on the device.
-    // Several ranks keep it only if every rank's check passed (each picks a class's entry at the same
-    // (x, y) of a shared plane, so the ranks' copies of the plane stay bitwise equal).
-    HIPCHK(setup_uniform_diag(c));
-    if (multi_rank(c)) {
-        const double mine = c->d_udiag ? 1.0 : 0.0;
-        double all = mine;
-        if (!c->d_small) c->d_small = dalloc<double>(8);
-        HIPCHK(hipMemcpyAsync(c->d_small, &mine, sizeof(double), hipMemcpyHostToDevice, c->stream));
-        comm_allreduce(c, c->d_small, 1);
-        HIPCHK(hipMemcpyAsync(&all, c->d_small, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (all != (double)c->nranks) dfree(c->d_udiag);
-    }
-    c->dinv_ready = true;
-}
-
-// the Jacobi scale in the order the running solve uses (mesh order, or the permuted SpMV order)
-const double *solver_dinv(cdfem_ctx *c)
-{
-    ensure_dinv(c);
-    if (!c->perm_space) return c->d_dinv;
-    if (!c->d_dinv_p) c->d_dinv_p = dalloc<double>(c->nl);
-    HIPCHK(launch_perm(c, true, c->d_dinv, c->d_dinv_p));
-    return c->d_dinv_p;
-}
-
-// cg_mr_fold all-reduces partial vectors, so every rank must take it and hold as many partials as the
-// others: the apply's (one per brick) and the update's (cg_den_fold_grid).  Decided by every rank of a
-// multi-rank solve from the all-reduced eligibility flags and the sums of the counts and of their
-// squares (equal on every rank, so every rank takes the same branch): the fold runs iff every rank is
-// eligible and the counts' variance is zero.  The 5-double all-reduce runs on EVERY multi-rank brick CG
-// entry, whatever the rank's local state (a cached decision let one rank skip the
-// collective after an option change that left its own key unchanged while another rank's key moved).
-bool mr_fold_agreed(cdfem_ctx *c)
-{
-    const double ok = cg_mr_fold(c) ? 1.0 : 0.0, nb = den_parts(c), ng = cg_den_fold_grid(c);
-    double h[5] = {ok, nb, nb * nb, ng, ng * ng};
-    if (!c->d_small) c->d_small = dalloc<double>(8);
-    HIPCHK(hipMemcpyAsync(c->d_small, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
-    comm_allreduce(c, c->d_small, 5);
-    HIPCHK(hipMemcpyAsync(h, c->d_small, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const double n = c->nranks;
-    return h[0] == n && h[2] * n == h[1] * h[1] && h[4] * n == h[3] * h[3];
-}
-
-// brick-path CG (MFEM CGSolver arithmetic): per iteration k_brick_cg (direction + apply + den
-// partials) -> den finalizer -> k_cg_update_faces (q assembly + x, r update + betanom partials) ->
-// betanom finalizer.  The search direction alternates between two buffers.
-void solve_cg_brick(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, double *dX,
-                    cdfem_solver_result &res)
-{
-    double *x = c->d_w[2], *r = c->d_w[3], *q = c->d_w[4];
-    if (!c->d_dalt) c->d_dalt = dalloc<double>(c->nl);
-    const int nbrick = brick_count(c);
-    if (!c->d_face) {  // (p = 3, 4: the blocks' patch buffer, first use)
-        const int S = brick_patch_side(c), SZ = brick_patch_side_z(c);
-        c->d_face = dalloc<double>((size_t)nbrick * S * S * SZ);
-    }
-    // the apply's den partials in two stages (a block per 1/256 of them, then one block) when the one
-    // block finalizer would sum too many: the p = 3, 4 blocks, and one rank past the den fold's bound
-    const int ndp = den_parts(c);  // the den partials the folds sum (grouped past the bounds: den_group)
-    const bool two_stage = c->p >= 3 || (!multi_rank(c) && ndp > kDenFoldMaxParts);
-    if (two_stage && !c->d_hbpart) c->d_hbpart = dalloc<double>(nbrick);
-    c->den_out = two_stage && c->p <= 2 ? c->d_hbpart : nullptr;
-    struct DenOutReset {
-        cdfem_ctx *c;
-        ~DenOutReset() { c->den_out = nullptr; c->den_grp = 1; }
-    } den_out_reset{c};
-    double *dprev = c->d_w[5], *dcur = c->d_dalt;
-    const double *dinv;
-    if (p.pc == CDFEM_PC_JACOBI) {
-        ensure_dinv(c);
-        dinv = c->d_dinv;
-    } else {
-        dinv = ones_vector(c);
-    }
-    const int check = p.check_every > 0 ? p.check_every : 16;
-    const bool mr = multi_rank(c);
-    double *red = c->d_state->red;  // device scalars awaiting the all-reduce
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (mr) {
-        HIPCHK(launch_cg_init_nofin(c, dB, x, r, q, dprev, dinv));
-        comm_allreduce(c, red + 2, 1);
-        HIPCHK(launch_init_step(c, p.rel_tol, p.abs_tol, p.max_iter));
-    } else {
-        HIPCHK(launch_cg_init(c, dB, x, r, q, dprev, dinv, p.rel_tol, p.abs_tol, p.max_iter));
-    }
-    // slab partition: the shared planes' partial sums come from the first and last brick layers
-    // only, so those layers run first on a side stream, whose pack + exchange then overlap the
-    // interior layers on the main stream.  Same kernels, same sums: bitwise equal
-    // to the one-launch form.  Profiling keeps the one-launch form (one timed apply kernel).
-    const bool overlap = mr && c->mr_overlap && !c->profile && c->p <= 2 && c->nbz >= 3;
-    if (overlap && !c->stream2) {
-        HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-        for (auto &e : c->ov_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    // x-fold (set_option "cg_xfold", default): every apply after the first advances x by the previous
-    // iteration's alpha d (the update kernel then streams neither x nor d); k_cg_xflush adds the
-    // last update's term after the loop when the update logic stopped the solve
-    const bool xfold = c->cg_xfold != 0 && pa_af(c) == 2;  // Kronecker kernel only
-    double *const dbuf0 = dcur, *const dbuf1 = dprev;  // apply j writes d_j into dbuf[(j - 1) & 1]
-    // betanom fold (cg_beta_fold): apply j > 0 takes the betanom step of update j - 1 (nupd updates so
-    // far); the loop always ends with an apply, so every update's step runs
-    // several ranks (cg_mr_fold): the den and betanom partial vectors are all-reduced and both folds
-    // run as on one rank; the per-iteration kernels are then the one-rank pair plus the plane pack
-    const bool mrfold = mr && mr_fold_agreed(c);
-    const bool bfold = mr ? mrfold : cg_beta_fold_ok(c);
-    // grouped den partials: taken when a fold sums them (several ranks: the fold; one rank: the den fold)
-    const int grp = (mr ? mrfold : (!two_stage && cg_den_fold_on(c))) ? den_group(c) : 1;
-    if (grp > 1 && c->gsum_cap < ndp) {
-        dfree(c->d_gsum);
-        dfree(c->d_gcnt);
-        c->d_gsum = dalloc<double>(ndp);
-        c->d_gcnt = dalloc<uint32_t>(ndp);
-        HIPCHK(hipMemsetAsync(c->d_gcnt, 0, (size_t)ndp * sizeof(uint32_t), c->stream));
-        c->gsum_cap = ndp;
-    }
-    c->den_grp = grp;
-    // cg_beta_sum: the betanom sum and the update's arrival counter (zeroed once: the last arriver resets it)
-    if (!mr && bfold && !c->d_bsum) {
-        c->d_bsum = dalloc<double>(2);
-        HIPCHK(hipMemsetAsync(c->d_bsum, 0, 2 * sizeof(double), c->stream));
-    }
-    double *const dparts = grp > 1 ? c->d_gsum : c->d_part;  // what the mr fold all-reduces (ndp of them)
-    int nupd = 0;
-    int napply = 0;
-    auto apply = [&] {
-        double *xf = (xfold && napply > 0) ? x : nullptr;
-        ++napply;
-        if (overlap) {
-            HIPCHK(hipEventRecord(c->ov_ev[0], c->stream));
-            HIPCHK(hipStreamWaitEvent(c->stream2, c->ov_ev[0], 0));
-            // boundary layers on the side stream, interior layers queued on the main stream
-            // before the (possibly host-blocking) exchange is issued
-            HIPCHK(launch_brick_cg2_split(c, r, dinv, dprev, dcur, q, c->stream2, xf, bfold ? nupd : -1));
-            HIPCHK(launch_pack_qplanes(c, q, c->stream2));
-            comm_exchange(c, c->d_if[0], c->d_if[1], c->d_if[2], c->d_if[3], c->Lx * c->Ly, c->stream2);
-            HIPCHK(hipEventRecord(c->ov_ev[1], c->stream2));
-            HIPCHK(hipStreamWaitEvent(c->stream, c->ov_ev[1], 0));
-            if (mrfold) {
-                comm_allreduce(c, dparts, ndp);  // the den partials: the update sums them
-            } else {
-                HIPCHK(launch_fin_sum(c, nbrick, 0));
-                comm_allreduce(c, red + 0, 1);  // den step: folded into the update kernel
-            }
-            return;
-        }
-        prof_mark(c, CDFEM_K_APPLY, true);
-        HIPCHK(launch_brick_cg2(c, r, dinv, dprev, dcur, q, xf, bfold ? nupd : -1));
-        prof_mark(c, CDFEM_K_APPLY, false);
-        prof_mark(c, CDFEM_K_E2L, true);
-        if (mr) {
-            // neighbours' partial sums of q on the shared planes (added by the update kernel)
-            HIPCHK(launch_pack_qplanes(c, q));
-            comm_exchange(c, c->d_if[0], c->d_if[1], c->d_if[2], c->d_if[3], c->Lx * c->Ly);
-            if (mrfold) {
-                comm_allreduce(c, dparts, ndp);
-            } else {
-                if (c->p >= 3) HIPCHK(launch_den_local_from_partials(c, c->d_hbpart, nbrick));  // (one per block)
-                else HIPCHK(launch_fin_sum(c, nbrick, 0));
-                comm_allreduce(c, red + 0, 1);  // den step: folded into the update kernel
-            }
-        } else if (two_stage) {
-            HIPCHK(launch_den_from_partials(c, c->d_hbpart, nbrick));  // (one partial per brick / block)
-        } else if (!cg_den_fold_on(c)) {
-            HIPCHK(launch_den_fin(c, nbrick));  // (cg_den_fold: the update kernel takes the den step)
-        }
-        prof_mark(c, CDFEM_K_E2L, false);
-    };
-    apply();
-    int launched = 0;
-    for (;;) {
-        for (int k = 0; k < check && launched < p.max_iter; ++k, ++launched) {
-            prof_mark(c, CDFEM_K_UPDATE, true);
-            HIPCHK(launch_cg_update_faces(c, x, r, q, dcur, dinv,
-                                          mr && c->zlo_shared ? c->d_if[1] : nullptr,
-                                          mr && c->zhi_shared ? c->d_if[3] : nullptr, mr && !mrfold, xfold));
-            if (mrfold) {
-                comm_allreduce(c, c->d_part + c->nblk, cg_den_fold_grid(c));  // the next apply sums them
-            } else if (mr) {
-                comm_allreduce(c, red + 1, 1);
-                HIPCHK(launch_update_step(c));
-            }
-            prof_mark(c, CDFEM_K_UPDATE, false);
-            ++nupd;
-            std::swap(dprev, dcur);
-            apply();
-        }
-        HIPCHK(hipMemcpyAsync(c->h_state, c->d_state, sizeof(KrylovState), hipMemcpyDeviceToHost,
-                              c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->h_state->done || launched >= p.max_iter) break;
-    }
-    if (xfold) {
-        HIPCHK(launch_cg_xflush(c, x, dbuf0, dbuf1));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    prof_collect(c);
-    const KrylovState &s = *c->h_state;
-    res.converged = s.converged;
-    res.iterations = s.final_iter;
-    res.initial_norm = std::sqrt(std::fabs(s.nom0));
-    res.final_norm = (s.final_iter == 0) ? std::sqrt(std::fabs(s.nom0)) : std::sqrt(std::fabs(s.betanom));
-    res.seconds = std::chrono::duration<double>(t1 - t0).count();
-    HIPCHK(hipMemcpyAsync(dX, x, c->nl * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-}
-
-// MFEM CGSolver on the constrained operator, device-resident
-void solve_cg(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, double *dX,
-              cdfem_solver_result &res)
-{
-    double *x = c->d_w[2], *r = c->d_w[3], *z = c->d_w[4], *d = c->d_w[5];
-    const double *dinv = p.pc == CDFEM_PC_JACOBI ? solver_dinv(c) : nullptr;
-    const int check = p.check_every > 0 ? p.check_every : 16;
-    const bool mr = multi_rank(c);
-    double *red = c->d_state->red;  // device scalars awaiting the all-reduce (multi-rank)
-    // high order on a structured box, one rank: den from the apply's E-vector, E->L fused into the
-    // update (ho_kernels.hip k_apply3d_tile<DEN>, vec_kernels.hip k_e2l_box<UPD>)
-    const bool fused = !mr && !c->fa_ready && c->cg_fused && tile_den_ok(c) && e2l_box_ok(c) &&
-                       c->nl < ((int64_t)1 << 31);  // the flat update's fast division is exact below 2^31
-    if (fused && !c->d_tpart) c->d_tpart = dalloc<double>(tile_den_blocks(c, true));
-    // direction fold (ho_dfold): apply j forms d_j = z + beta d_{j-1} into the other direction buffer
-    const bool dfold = fused && tile_dfold_ok(c);
-    if (dfold && !c->d_dalt) c->d_dalt = dalloc<double>(c->nl);
-    double *dprev = d, *dcur = dfold ? c->d_dalt : d;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (mr) {
-        HIPCHK(launch_cg_init_nofin(c, dB, x, r, z, d, dinv));
-        comm_allreduce(c, red + 2, 1);
-        HIPCHK(launch_init_step(c, p.rel_tol, p.abs_tol, p.max_iter));
-    } else {
-        HIPCHK(launch_cg_init(c, dB, x, r, z, d, dinv, p.rel_tol, p.abs_tol, p.max_iter));
-    }
-    // z = A d ; den = (d, z) and the MFEM den step
-    auto apply = [&] {
-        prof_mark(c, CDFEM_K_APPLY, true);
-        if (fused) {  // Ye = A_c d and den; q stays an E-vector until the update
-            if (dfold) HIPCHK(launch_apply_den_dfold(c, z, dprev, dcur, c->d_Ye, c->d_state, c->d_tpart));
-            else HIPCHK(launch_apply_den(c, d, c->d_Ye, c->d_state, c->d_tpart));
-            prof_mark(c, CDFEM_K_APPLY, false);
-            prof_mark(c, CDFEM_K_E2L, true);
-            HIPCHK(launch_den_from_partials(c, c->d_tpart, tile_den_blocks(c)));
-            prof_mark(c, CDFEM_K_E2L, false);
-            return;
-        }
-        if (c->fa_ready && !mr) {
-            HIPCHK(launch_spmv_cg(c, d, z));
-            prof_mark(c, CDFEM_K_APPLY, false);
-            return;
-        }
-        if (c->fa_ready) HIPCHK(launch_spmv(c, true, d, z));
-        else HIPCHK(launch_apply_st(c, d, c->d_Ye, true, c->d_state));
-        prof_mark(c, CDFEM_K_APPLY, false);
-        prof_mark(c, CDFEM_K_E2L, true);
-        if (mr) {  // rank partition: interface sums, essential rows reset, owned den all-reduced
-            if (!c->fa_ready) HIPCHK(launch_e2l(c, c->d_Ye, d, z, true, 0));
-            interface_sum(c, z);
-            HIPCHK(launch_set_ess(c, z, d));
-            HIPCHK(launch_den_local(c, d, z));
-            comm_allreduce(c, red + 0, 1);
-            HIPCHK(launch_den_step(c));
-        } else {
-            HIPCHK(launch_e2l(c, c->d_Ye, d, z, true, 1));
-        }
-        prof_mark(c, CDFEM_K_E2L, false);
-    };
-    apply();
-    int launched = 0;
-    for (;;) {
-        for (int k = 0; k < check && launched < p.max_iter; ++k, ++launched) {
-            prof_mark(c, CDFEM_K_UPDATE, true);
-            if (fused) HIPCHK(launch_e2l_cg_update(c, c->d_Ye, dcur, x, r, z, dinv));
-            else HIPCHK(launch_cg_update(c, x, r, z, d, dinv));
-            if (mr) {
-                comm_allreduce(c, red + 1, 1);
-                HIPCHK(launch_update_step(c));
-            }
-            prof_mark(c, CDFEM_K_UPDATE, false);
-            if (dfold) {
-                std::swap(dprev, dcur);
-            } else {
-                prof_mark(c, CDFEM_K_DIRECTION, true);
-                HIPCHK(launch_cg_direction(c, z, d));
-                prof_mark(c, CDFEM_K_DIRECTION, false);
-            }
-            apply();
-        }
-        HIPCHK(hipMemcpyAsync(c->h_state, c->d_state, sizeof(KrylovState), hipMemcpyDeviceToHost,
-                              c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->h_state->done || launched >= p.max_iter) break;
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    prof_collect(c);
-    const KrylovState &s = *c->h_state;
-    res.converged = s.converged;
-    res.iterations = s.final_iter;
-    res.initial_norm = std::sqrt(std::fabs(s.nom0));
-    res.final_norm = (s.final_iter == 0) ? std::sqrt(std::fabs(s.nom0)) : std::sqrt(std::fabs(s.betanom));
-    res.seconds = std::chrono::duration<double>(t1 - t0).count();
-    HIPCHK(hipMemcpyAsync(dX, x, c->nl * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-}
-
-// PETSc KSPGMRES(m) + left Jacobi on the constrained operator (gmres.hip).  One host sync per
-// restart cycle plus a lag-one poll inside the cycle: step j + 1 is queued before the host waits
-// for step j's flags, so the GPU never idles on the host; a step queued past the end of a cycle
-// costs one wasted operator apply (its GMRES kernels exit at entry).
-void solve_gmres(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, double *dX,
-                 cdfem_solver_result &res)
-{
-    const int m = p.restart > 0 ? p.restart : 30;
-    if (m > kGmMaxRestart) throw ArgError("restart > 64");
-    const int64_t n = c->nl;
-    // basis leading dimension padded to 32 doubles: every basis vector starts on a 256-byte
-    // boundary, so a wave's 512-byte load of v_i covers 4 cache lines, not 5 (odd n)
-    const int64_t ldv = (n + 31) / 32 * 32;
-    const int nb = gmres_blocks(n);
-    if (c->gm_cap < m) {
-        dfree(c->d_gm);
-        dfree(c->d_gm_part);
-        c->d_gm = dalloc<double>((size_t)(m + 1) * ldv);
-        c->d_gm_part = dalloc<double>((size_t)(m + 1) * nb);
-        c->gm_cap = m;
-    }
-    if (!c->d_gmst) {
-        HIPCHK(hipMalloc(&c->d_gmst, sizeof(GmresState)));
-        // poll slots: 0 for the cycle start / end, 1 + j for inner step j (each step its own slot, so a
-        // host check reads exactly the state of the step it waited for: ranks decide alike)
-        HIPCHK(hipHostMalloc(&c->h_gmpoll, (kGmMaxRestart + 1) * sizeof(GmresState), hipHostMallocDefault));
-        for (auto &e : c->gm_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    const double *dinv = nullptr;
-    const bool ilu = p.pc == CDFEM_PC_ILU;
-    if (p.pc == CDFEM_PC_JACOBI) {
-        dinv = solver_dinv(c);
-    } else if (ilu) {
-        if (!c->fa_ready) throw UnsupportedError("ILU(0) needs an assembled operator (cdfem_fa_setup)");
-        if (multi_rank(c) && c->part_mode != 2)
-            throw UnsupportedError("block-Jacobi ILU(0) needs a general partition (cdfem_set_shared)");
-        ilu_setup(c);
-    }
-    double *x = c->d_w[2], *w = c->d_w[4], *V = c->d_gm, *part = c->d_gm_part;
-    GmresState *st = c->d_gmst, *poll = c->h_gmpoll;
-    // the step's last scalar kernel has written poll[slot] (post_poll in gmres.hip); the event
-    // marks its completion for the host.  (Measured alternatives, profiles/r03/ab_c2_gmres_poll.txt:
-    // spinning on a stamp in pinned memory, 392.2 / 392.0 against 392.3 us per C2 step; polling every
-    // 2 / 4 / 30 steps, 390.3 / 388.4 / 388.0 against 391.5: the host wait is not on the critical path.)
-    auto post = [&](int slot) { HIPCHK(hipEventRecord(c->gm_ev[slot], c->stream)); };
-    auto wait = [&](int slot) -> const GmresState & {
-        HIPCHK(hipEventSynchronize(c->gm_ev[slot]));
-        return poll[slot];
-    };
-    // one rank on the structured patch-buffer Mult: pass 1 forms A_c v_j from the patch buffer itself
-    const bool gpb = c->gm_pb != 0 && !ilu && !multi_rank(c) && use_brick(c) && brick_mult_pb_on(c);
-    // gm_poll k (default 4): an event and a host check every k inner steps (and at a cycle's last step)
-    // instead of every step: each event costs the GPU ~5 us before the next Mult (rocprofv3 trace gaps,
-    // profiles/r06/ab_gmres_poll/; C2 step 181.3-182.8 -> 178.1-178.2 us at k = 4).  Every step's last
-    // scalar kernel posts the state head into its own slot poll[1 + j]; a check waits for the previous
-    // check's event and reads exactly that step's slot, never a later step's (on several ranks every rank
-    // must leave the loop at the same step: their collectives pair up).  Steps queued past the end of a
-    // cycle exit at entry (their Mult does not check, and runs at most k - 1 times per converged cycle).
-
-    const int pk = std::max(1, c->gm_poll);
-    int nposts = 0, last_posted = -1;
-    auto step_end = [&](int j, bool cycle_last) -> bool {  // true: the cycle is done, leave the step loop
-        if (!cycle_last && (j + 1) % pk != 0) return false;
-        post(nposts & 1);
-        const int prev = last_posted;
-        last_posted = j;
-        ++nposts;
-        if (nposts < 2 || prev < 0) return false;
-        HIPCHK(hipEventSynchronize(c->gm_ev[(nposts - 2) & 1]));  // the previous check's event
-        return poll[1 + prev].cycle_done != 0;                      // exactly its step's state
-    };
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipMemsetAsync(x, 0, n * sizeof(double), c->stream));
-    HIPCHK(launch_gm_init(c, st, m, p.max_iter));
-    for (bool first = true;; first = false) {
-        // v0 = M^{-1}(b - A x); x = 0 on the first cycle, so A x is skipped there
-        if (!first) op_apply_global(c, x, w, true);
-        if (ilu) {  // v0 = (LU)^{-1} (b - A x): the residual into w, the sweeps into ilu.z
-            if (first) HIPCHK(hipMemcpyAsync(w, dB, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-            else HIPCHK(launch_axpby(c, 1.0, dB, -1.0, w));
-            HIPCHK(ilu_apply(c));
-            HIPCHK(launch_gm_residual(c, c->ilu.z, nullptr, nullptr, V, part, st, first, p.rel_tol, p.abs_tol,
-                                      &poll[0]));
-        } else {
-            HIPCHK(launch_gm_residual(c, dB, first ? nullptr : w, dinv, V, part, st, first, p.rel_tol, p.abs_tol,
-                                      &poll[0]));
-        }
-        post(0);
-        if (wait(0).done) break;
-        for (int j = 0; j < m; ++j) {
-            const double *Vj = V + (int64_t)j * ldv;
-            if (gpb) {  // the structured Mult's patch buffer, summed per row by pass 1 (gm_pb)
-                prof_mark(c, CDFEM_K_APPLY, true);
-                HIPCHK(launch_brick_mult(c, Vj, w, true, 1));
-                prof_mark(c, CDFEM_K_APPLY, false);
-                const GmPatchSrc src = gm_patch_src(c, Vj);
-                prof_mark(c, CDFEM_K_ORTH, true);
-                HIPCHK(launch_gm_orth(c, w, dinv, V, ldv, part, st, m, &poll[1 + j], &src));
-                prof_mark(c, CDFEM_K_ORTH, false);
-                if (step_end(j, j == m - 1)) break;
-                continue;
-            }
-            op_apply_global(c, Vj, w, true);
-            if (ilu) HIPCHK(ilu_apply(c));  // w <- (LU)^{-1} A v_j, in ilu.z
-            prof_mark(c, CDFEM_K_ORTH, true);
-            HIPCHK(launch_gm_orth(c, ilu ? c->ilu.z : w, dinv, V, ldv, part, st, m, &poll[1 + j]));
-            prof_mark(c, CDFEM_K_ORTH, false);
-            if (step_end(j, j == m - 1)) break;
-        }
-        nposts = 0;
-        last_posted = -1;
-        prof_mark(c, CDFEM_K_UPDATE, true);
-        HIPCHK(launch_gm_update(c, x, V, ldv, st, &poll[0]));
-        prof_mark(c, CDFEM_K_UPDATE, false);
-        post(0);
-        if (wait(0).done) break;
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    prof_collect(c);
-    GmresState fin{};
-    HIPCHK(hipMemcpy(&fin, st, sizeof(GmresState), hipMemcpyDeviceToHost));
-    res.converged = fin.converged;
-    res.iterations = fin.its;
-    res.initial_norm = fin.res0;
-    res.final_norm = fin.res;
-    res.seconds = std::chrono::duration<double>(t1 - t0).count();
-    HIPCHK(hipMemcpyAsync(dX, x, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-}
-
-// PETSc KSPBCGS + left preconditioning on the constrained operator (bicgstab.hip): seven L-vectors, two
-// operator applies per iteration, no orthogonalisation.  The host queues iterations without waiting
-// for the device: every check_every-th iteration's last scalar kernel posts the head of the state into
-// the pinned slot (i / check_every) % kBcgsSlots, a function of the iteration number alone and so the
-// same on every rank, and the host reads a posted iteration's slot one check later, after the next
-// check_every iterations are queued (the lag-one poll of solve_gmres).  A slot is rewritten kBcgsSlots
-// checks later, after the host has read it, so a check reads the state of exactly the iteration it names;
-// the all-reduced sums make that state the same on every rank, so every rank leaves the loop at the same
-// iteration and their collectives pair up.  Past the stop every solver kernel exits at entry; the applies
-// do not check: a stop at iteration s is posted by the next polled iteration q < s + check_every and read
-// after iteration q + check_every is queued, so at most 2 check_every - 1 iterations, that is
-// 2 (2 check_every - 1) operator applies, run past the stop (and never more than max_iter iterations in all).
-void solve_bicgstab(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, double *dX,
-                    cdfem_solver_result &res)
-{
-    const int64_t n = c->nl;
-    const int64_t ldv = (n + 31) / 32 * 32;  // every vector on a 256-byte boundary
-    const int nb = bcgs_blocks(n);
-    if (c->bcgs_n != n || !c->d_bcgs) {
-        dfree(c->d_bcgs);
-        dfree(c->d_bcgs_part);
-        c->d_bcgs = dalloc<double>((size_t)6 * ldv);
-        c->d_bcgs_part = dalloc<double>((size_t)3 * nb);
-        c->bcgs_n = n;
-    }
-    if (!c->d_bcst) {
-        HIPCHK(hipMalloc(&c->d_bcst, sizeof(BcgsState)));
-        HIPCHK(hipHostMalloc(&c->h_bcpoll, (kBcgsSlots + 1) * sizeof(BcgsState), hipHostMallocDefault));
-        for (auto &e : c->bc_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    const double *dinv = nullptr;
-    const bool ilu = p.pc == CDFEM_PC_ILU;
-    if (p.pc == CDFEM_PC_JACOBI) {
-        dinv = solver_dinv(c);
-    } else if (ilu) {
-        if (!c->fa_ready) throw UnsupportedError("ILU(0) needs an assembled operator (cdfem_fa_setup)");
-        if (multi_rank(c) && c->part_mode != 2)
-            throw UnsupportedError("block-Jacobi ILU(0) needs a general partition (cdfem_set_shared)");
-        ilu_setup(c);
-    }
-    double *x = c->d_bcgs, *r = x + ldv, *rh = r + ldv, *pv = rh + ldv, *v = pv + ldv, *t = v + ldv;
-    double *w = c->d_w[4], *part = c->d_bcgs_part;  // w: the apply's output (and ilu_apply's input)
-    BcgsState *st = c->d_bcst, *poll = c->h_bcpoll;
-    // one rank on the structured patch-buffer Mult: k_bcgs_v / k_bcgs_t form A_c u from the patch buffer
-    // itself (GMRES's predicate, set_option "gm_pb")
-    const bool gpb = c->gm_pb != 0 && !ilu && !multi_rank(c) && use_brick(c) && brick_mult_pb_on(c);
-    c->bcgs_src = gpb ? kBrick * c->p + 1 : 0;
-    c->bcgs_diag = dinv ? 1 : 0;
-    const int ce = p.check_every > 0 ? p.check_every : 16;
-    // w = A_c u, or phase 1 of the structured Mult alone (the patch buffer is the result); then M^{-1}
-    auto mult = [&](const double *u) -> const double * {
-        if (gpb) {
-            prof_mark(c, CDFEM_K_APPLY, true);
-            HIPCHK(launch_brick_mult(c, u, w, true, 1));
-            prof_mark(c, CDFEM_K_APPLY, false);
-            return w;
-        }
-        op_apply_global(c, u, w, true);
-        if (!ilu) return w;
-        HIPCHK(ilu_apply(c));  // ilu.z = (LU)^{-1} w
-        return c->ilu.z;
-    };
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipMemsetAsync(x, 0, n * sizeof(double), c->stream));
-    HIPCHK(hipMemsetAsync(pv, 0, n * sizeof(double), c->stream));
-    HIPCHK(hipMemsetAsync(v, 0, n * sizeof(double), c->stream));
-    const double *b0 = dB;
-    if (ilu) {  // r = (LU)^{-1} B
-        HIPCHK(hipMemcpyAsync(w, dB, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(ilu_apply(c));
-        b0 = c->ilu.z;
-    }
-    prof_mark(c, CDFEM_K_UPDATE, true);
-    HIPCHK(launch_bcgs_init(c, b0, dinv, r, rh, part, st, p.rel_tol, p.abs_tol, p.max_iter, &poll[kBcgsSlots]));
-    prof_mark(c, CDFEM_K_UPDATE, false);
-    HIPCHK(hipEventRecord(c->bc_ev[0], c->stream));
-    HIPCHK(hipEventSynchronize(c->bc_ev[0]));
-    int nchecks = 0, prev_slot = -1;
-    for (int i = 0; i < p.max_iter && !poll[kBcgsSlots].done; ++i) {
-        const bool polled = (i + 1) % ce == 0;
-        const int slot = (i / ce) % kBcgsSlots;
-        prof_mark(c, CDFEM_K_UPDATE, true);
-        HIPCHK(launch_bcgs_p(c, r, pv, v, st));
-        prof_mark(c, CDFEM_K_UPDATE, false);
-        const double *ap = mult(pv);
-        const GmPatchSrc srcp = gpb ? gm_patch_src(c, pv) : GmPatchSrc{};
-        prof_mark(c, CDFEM_K_UPDATE, true);
-        HIPCHK(launch_bcgs_v(c, ap, dinv, rh, v, r, part, st, gpb ? &srcp : nullptr));
-        prof_mark(c, CDFEM_K_UPDATE, false);
-        const double *as = mult(r);
-        const GmPatchSrc srcs = gpb ? gm_patch_src(c, r) : GmPatchSrc{};
-        prof_mark(c, CDFEM_K_UPDATE, true);
-        HIPCHK(launch_bcgs_t(c, as, dinv, x, pv, r, t, rh, part, st, polled ? &poll[slot] : nullptr,
-                             gpb ? &srcs : nullptr));
-        prof_mark(c, CDFEM_K_UPDATE, false);
-        if (!polled) continue;
-        HIPCHK(hipEventRecord(c->bc_ev[nchecks & 1], c->stream));
-        const int prev = prev_slot;
-        prev_slot = slot;
-        ++nchecks;
-        if (prev < 0) continue;
-        HIPCHK(hipEventSynchronize(c->bc_ev[nchecks & 1]));  // the previous check's event
-        if (poll[prev].done) break;                           // exactly its iteration's state
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const auto t1 = std::chrono::steady_clock::now();
-    prof_collect(c);
-    BcgsState fin{};
-    HIPCHK(hipMemcpy(&fin, st, sizeof(BcgsState), hipMemcpyDeviceToHost));
-    res.converged = fin.converged;
-    res.iterations = fin.its;
-    res.initial_norm = fin.res0;
-    res.final_norm = fin.dp;
-    res.seconds = std::chrono::duration<double>(t1 - t0).count();
-    if (fin.breakdown)
-        c->err = fin.breakdown == kBcgsBreakRho  ? "BiCGStab breakdown: rho = (r, rh) is zero"
-                 : fin.breakdown == kBcgsBreakD1 ? "BiCGStab breakdown: (v, rh) is zero"
-                                                 : "BiCGStab breakdown: (t, t) is zero with a nonzero s";
-    HIPCHK(hipMemcpyAsync(dX, x, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-}
 
 }  // namespace
-
-// ho_uniform: the block CG applies the common element matrix on the matrix cores (k_hobrick_um); the
-// matrix is the PA setup's, for the order and kinds it was formed for, on 2 x 2 x 4 blocks of one rank
-// (shared with hobrick_um.hip and brick_kernels.hip)
-bool cdfem::ho_uniform_path(const cdfem_ctx *c)
-{
-    return c->ho_uniform != 0 && (c->kinds == 7 || c->kinds == 5) && !multi_rank(c) && c->hb_ez == 4 && use_hobrick_cg(c);
-}
-bool cdfem::ho_uniform_elem(const cdfem_ctx *c)
-{
-    return c->d_hoelem != nullptr && c->hoelem_p == c->p && c->hoelem_kinds == c->kinds && ho_uniform_path(c);
-}
 
 // ================================================================================================
 extern "C" {
@@ -1966,16 +1251,7 @@ int cdfem_solve(cdfem_ctx *c, const cdfem_solver_params *p, const double *B, dou
             dXs = c->d_pv[1];
             c->perm_space = true;
         }
-        if (p->method == CDFEM_CG) {
-            if (use_brick_cg(c))
-                solve_cg_brick(c, *p, dBs, dXs, *res);
-            else
-                solve_cg(c, *p, dBs, dXs, *res);
-        } else if (p->method == CDFEM_BICGSTAB) {
-            solve_bicgstab(c, *p, dBs, dXs, *res);
-        } else {
-            solve_gmres(c, *p, dBs, dXs, *res);
-        }
+        solve(c, *p, dBs, dXs, *res);
         if (pspace) {
             c->perm_space = false;
             HIPCHK(launch_perm(c, false, dXs, dX));
@@ -2049,127 +1325,8 @@ int cdfem_fp64_bench(cdfem_ctx *c, int mode, int reps, double *tflops)
 int cdfem_set_option(cdfem_ctx *c, const char *key, int value)
 {
     return guarded(c, [&] {
-        if (!key) throw ArgError("key is null");
-        const std::string k(key);
-        if (k == "brick_xcd") {
-            if (value < 0 || value > 1) throw ArgError("brick_xcd must be 0 or 1");
-            c->brick_xcd = value;
-        } else if (k == "brick_byte_limit") {
-            if (value < 0) throw ArgError("brick_byte_limit must be 0 (the default 2^31) or 1..2^31-1");
-            c->brick_limit = value == 0 ? (int64_t)1 << 31 : value;
-        } else if (k == "den_group") {
-            if (value < 0 || value > 64 || (value & (value - 1)) != 0)
-                throw ArgError("den_group must be 0 (automatic) or a power of two up to 64");
-            c->den_group_opt = value;
-        } else if (k == "cg_mr_fold") {
-            if (value != 0 && value != 1) throw ArgError("cg_mr_fold must be 0 or 1");
-            c->cg_mr_fold = value;
-        } else if (k == "ho_brick_mfma") {
-            if (value != 0 && value != 1) throw ArgError("ho_brick_mfma must be 0 or 1");
-            c->ho_brick_mfma = value;
-        } else if (k == "brick_stagger") {
-            if (value < -1 || value > 511) throw ArgError("brick_stagger must be -1 (automatic), 0 (off) or 1..511");
-            c->brick_stagger = value;
-        } else if (k == "pa_uniform") {  // the matrix is formed by cdfem_pa_setup; 0 leaves it unused
-            if (value != 0 && value != 1) throw ArgError("pa_uniform must be 0 or 1");
-            c->pa_uniform = value;
-        } else if (k == "pa_uniform_diag") {  // the table is built with the Jacobi scale; 0 leaves it unused
-            if (value != 0 && value != 1) throw ArgError("pa_uniform_diag must be 0 or 1");
-            c->pa_uniform_diag = value;
-        } else if (k == "ho_uniform") {  // the matrix is formed by cdfem_pa_setup when 1; 0 leaves it unused
-            if (value != 0 && value != 1) throw ArgError("ho_uniform must be 0 or 1");
-            c->ho_uniform = value;
-        } else if (k == "ho_uniform_grid") {
-            if (value < 0) throw ArgError("ho_uniform_grid must be 0 (automatic) or the number of workgroups");
-            c->ho_uniform_grid = value;
-        } else if (k == "brick_mfma") {
-            if (value != 0 && value != 1) throw ArgError("brick_mfma must be 0 or 1");
-            c->brick_mfma = value;
-        } else if (k == "ho_block_z") {  // read by cdfem_mesh_set_structured
-            if (value != 2 && value != 4) throw ArgError("ho_block_z must be 2 or 4");
-            c->ho_block_z = value;
-        } else if (k == "ho_brick") {
-            if (value != 0 && value != 1) throw ArgError("ho_brick must be 0 or 1");
-            c->ho_brick = value;
-        } else if (k == "mr_overlap") {
-            if (value < 0 || value > 1) throw ArgError("mr_overlap must be 0 or 1");
-            c->mr_overlap = value;
-        } else if (k == "brick_mult_pb") {
-            if (value != 0 && value != 1) throw ArgError("brick_mult_pb must be 0 or 1");
-            c->brick_mult_pb = value;
-        } else if (k == "cg_beta_fold") {
-            if (value != 0 && value != 1) throw ArgError("cg_beta_fold must be 0 or 1");
-            c->cg_beta_fold = value;
-        } else if (k == "cg_beta_sum") {
-            if (value != 0 && value != 1) throw ArgError("cg_beta_sum must be 0 or 1");
-            c->cg_beta_sum = value;
-        } else if (k == "cg_den_fold") {
-            if (value != 0 && (value < 64 || value > 16384)) throw ArgError("cg_den_fold must be 0 or 64..16384");
-            c->cg_den_fold = value;
-        } else if (k == "brick_upd_pb") {
-            if (value != 0 && value != 1) throw ArgError("brick_upd_pb must be 0 or 1");
-            c->brick_upd_pb = value;
-        } else if (k == "ho_dfold") {
-            if (value != 0 && value != 1) throw ArgError("ho_dfold must be 0 or 1");
-            c->ho_dfold = value;
-        } else if (k == "ho_mfma") {
-            if (value != 0 && value != 1 && value != 3 && value != 8 && value != 9 && value != 15)
-                throw ArgError("ho_mfma must be 0, 1, 3, 8, 9 or 15");
-            c->ho_mfma = value;
-        } else if (k == "cg_xfold") {
-            if (value != 0 && value != 1) throw ArgError("cg_xfold must be 0 or 1");
-            c->cg_xfold = value;
-        } else if (k == "cg_fused") {
-            if (value < 0 || value > 1) throw ArgError("cg_fused must be 0 or 1");
-            c->cg_fused = value;
-        } else if (k == "sell_order") {  // read when the FA pattern is built (once per mesh)
-            if (value < 0 || value > 8)
-                throw ArgError("sell_order must be 0..8 (0 natural, 1 natural + windows, 2 RCM + windows, 3 auto, 4 RCM, 5 geometric, 6 Morton + windows, 7 Morton, 8 Morton LDS windows / auto)");
-            c->sell_mode = value;
-        } else if (k == "gm_poll") {
-            if (value < 1 || value > 64) throw ArgError("gm_poll must be 1..64");
-            c->gm_poll = value;
-        } else if (k == "gm_pb") {
-            if (value < 0 || value > 1) throw ArgError("gm_pb must be 0 or 1");
-            c->gm_pb = value;
-        } else if (k == "pa_affine") {  // read by cdfem_pa_setup
-            if (value < 0 || value > 2) throw ArgError("pa_affine must be 0, 1 or 2");
-            c->pa_affine = value;
-        } else if (k == "pa_geom") {  // read by cdfem_pa_setup; 0 afterwards switches back to the stream
-            // (3D hex p <= 2 applies k_apply3d, k_brick3d, k_brick_cg; the p = 3, 4 tile kernels and the 2D
-            // applies keep the stream)
-            if (value != 0 && value != 1) throw ArgError("pa_geom must be 0 or 1");
-            c->pa_geom = value;
-        } else if (k == "ho_geom") {  // read by cdfem_pa_setup; 0 afterwards switches back to the stream
-            // (the 3D hex p = 3, 4 tile apply k_apply3d_tile where it runs the stream with ho_mfma 0)
-            if (value != 0 && value != 1) throw ArgError("ho_geom must be 0 or 1");
-            c->ho_geom = value;
-        } else if (k == "spmv_lpr") {  // read when the FA pattern is built (once per mesh)
-            if (value != 0 && value != 1 && value != 2 && value != 4) throw ArgError("spmv_lpr must be 0 (auto), 1, 2 or 4");
-            c->spmv_lpr = value;
-        } else if (k == "spmv_lds") {  // read when the FA pattern is built (once per mesh)
-            if (value < -1 || (value > 0 && (value % 64 != 0 || value > 65536)))
-                throw ArgError("spmv_lds must be -1 (auto), 0 (off) or rows per window, a multiple of 64 up to 65536");
-            c->spmv_lds = value;
-        } else if (k == "sell_window") {  // read when the FA pattern is built (once per mesh)
-            if (value < 0 || (value > 0 && (value % 64 != 0 || value > (1 << 20))))
-                throw ArgError("sell_window must be 0 (auto) or a multiple of 64 up to 2^20");
-            c->sell_window = value;
-        } else if (k == "gm_ept") {
-            if (value != 0 && value != 4 && value != 5 && value != 6 && value != 8)
-                throw ArgError("gm_ept must be 0 (auto), 4, 5, 6 or 8");
-            c->gm_ept = value;
-        } else if (k == "spmv_xcd") {
-            if (value < 0 || value > 1) throw ArgError("spmv_xcd must be 0 or 1");
-            c->spmv_xcd = value;
-        } else if (k == "spmv_index16") {
-            if (value < 0 || value > 1) throw ArgError("spmv_index16 must be 0 or 1");
-            c->spmv_index16 = value;
-        } else if (k == "profile_mask") {
-            c->prof_mask = (unsigned)value;
-        } else {
-            throw ArgError("unknown option " + k);
-        }
+        const std::string refusal = set_option(*c, key, value);
+        if (!refusal.empty()) throw ArgError(refusal);
         return CDFEM_OK;
     });
 }
@@ -2218,26 +1375,13 @@ int cdfem_profile_launches(cdfem_ctx *c, int k, double *ms, int64_t cap, int64_t
     });
 }
 
-// name of the HIP kernel that kernel id runs as in the current configuration (rocprof's kernel
-// name without its template arguments): the apply of a CG solve (the roofline kernel of the bench)
+// the cost model (model.hip)
 int cdfem_kernel_name(cdfem_ctx *c, int k, char *buf, size_t n)
 {
     return guarded(c, [&] {
         require_pa(c);
         if (!buf || n == 0) throw ArgError("buffer is null");
-        if (k == CDFEM_K_UPDATE && c->last_method == CDFEM_BICGSTAB) {
-            // the last BiCGStab solve's operator source: the Mult's output (S=0) or the patch buffer (S=4p+1)
-            std::snprintf(buf, n, "k_bcgs_v<S=%d>", c->bcgs_src);
-            return CDFEM_OK;
-        }
-        if (k != CDFEM_K_APPLY) throw UnsupportedError("kernel names: the operator apply only");
-        const char *name = c->fa_ready ? (c->lds_rows > 0 ? "k_sell_spmv_lds" : "k_sell_spmv")
-                           : use_brick(c) ? "k_brick_cg"
-                           : ho_uniform_elem(c) ? "k_hobrick_um"
-                           : use_hobrick_cg(c) ? "k_hobrick_cg"
-                           : c->qlay == 1 ? (tile_kron(c) ? "k_apply3d_ktile" : "k_apply3d_tile")
-                                          : "k_apply3d";
-        std::snprintf(buf, n, "%s", name);
+        kernel_name(c, k, buf, n);
         return CDFEM_OK;
     });
 }
@@ -2247,82 +1391,7 @@ int cdfem_kernel_flops(cdfem_ctx *c, int k, double *flops)
     return guarded(c, [&] {
         require_pa(c);
         if (!flops) throw ArgError("flops is null");
-        if (k != CDFEM_K_APPLY || c->fa_ready || c->dim != 3)
-            throw UnsupportedError("kernel flops: the 3D partial-assembly apply only");
-        // sum factorization, one element (pa_core.hpp elem_apply3d): per z plane the z contraction
-        // (D^3 FMA per field), per (z, y) the y contraction, per point the x contraction, the
-        // point operator and the transposed x contraction, then the transposed y and z contractions.
-        // Fields: value, plus the three reference derivatives when diffusion or convection is on.
-        const int D = c->d1, Q = c->rule_op.q1;
-        const bool kD = c->kinds & CDFEM_DIFFUSION, kC = c->kinds & CDFEM_CONVECTION, kM = c->kinds & CDFEM_MASS;
-        if (c->qlay == 0 && uniform_elem(c) && use_brick(c)) {
-            // the common element matrix (brick_um.hip k_brick_cg<XF, BF, FULL>): nd^2 MACs per element (the MFMA tiles'
-            // zero padding, 56 x 1024 MACs per 64 elements against 64 x 729, is not counted)
-            *flops = 2.0 * (double)c->nd * c->nd * (double)c->ne;
-            return CDFEM_OK;
-        }
-        if (c->qlay == 1 && ho_uniform_elem(c)) {  // k_hobrick_um: the same count (padding to 128 x 128 not counted)
-            *flops = 2.0 * (double)c->nd * c->nd * (double)c->ne;
-            return CDFEM_OK;
-        }
-        if ((c->qlay == 0 && pa_af(c) == 2) || (c->qlay == 1 && tile_kron(c))) {
-            // Kronecker form (pa_core.hpp elem_apply3d_kron; the tile kernel k_apply3d_ktile runs the
-            // same stages across threads), per input z plane: a length-n linear combination counts
-            // 2n - 1 flops, an accumulation into Y 2 per term
-            const bool kG = kD || kC;
-            auto lc = [](int n) { return n > 0 ? 2.0 * n - 1.0 : 0.0; };
-            const double x_row = lc(D) * (1 + 2 * kD + kG) + lc(kM + kD + kC) + 2 * lc(kD + kC);
-            double y_pt = lc(D) + (kG ? 2 * lc(D) + 1 : 0.0);
-            if (kD) y_pt += 6 * lc(D) + 2 + 2 + 1 + 2 + 3;
-            const double z_pt = 2.0 * (1 + 2 * kD + kG) * D;
-            *flops = (double)D * ((double)D * D * x_row + (double)D * D * (y_pt + z_pt)) * (double)c->ne;
-            return CDFEM_OK;
-        }
-        const int g = (kD || kC) ? 1 : 0;
-        double pt_fma = D * (1 + 3 * g) + D * (kD ? 4 : 1), pt_mul = 0.0;  // x contraction, transposed x
-        if (kD) { pt_fma += 6; pt_mul += 3; }
-        if (kC) { pt_fma += 2; pt_mul += 1; }
-        if (kM) { if (kC) pt_fma += 1; else pt_mul += 1; }
-        if (c->qlay == 1 ? tile_affine(c) : c->d_qaff != nullptr)
-            pt_mul += c->ncomp + 2;  // point data W_q * g_k, W_q = (w_x w_y) w_z
-        double geo_fma = 0.0;  // pa_geom: the hoisted parts of J, 9 FMAs per (z, y) and 9 per z plane
-        if (c->qlay == 0 && pa_geom_on(c)) {
-            // the point operator of elem_apply3d<..., GEO> instead of the one above: two columns of J
-            // (6 FMA), adj(J) (a mul and an FMA per entry; its first row alone without diffusion and
-            // convection), det J (1 mul, 2 FMA), W_q (2 mul); t = adj(J)^T grad u (3 mul, 6 FMA);
-            // D: W kappa / det J (2 mul, the reciprocal counted as 1 division), the scaled t (3 mul),
-            // adj(J) t (3 mul, 6 FMA); C: W (alpha c . t) (2 mul, 2 FMA); M: W s det J (2 mul) and its
-            // product with u (an FMA after C, else a mul)
-            const int na = g ? 9 : 3;
-            pt_fma = D * (1 + 3 * g) + D * (kD ? 4 : 1);
-            pt_mul = 0.0;
-            pt_fma += 6 + na + 2 + (g ? 6 : 0) + (kD ? 6 : 0) + (kC ? 2 : 0) + ((kM && kC) ? 1 : 0);
-            pt_mul += na + 1 + 2 + (g ? 3 : 0) + (kD ? 2 + 1 + 3 + 3 : 0) + (kC ? 2 : 0) + (kM ? 2 : 0) +
-                      ((kM && !kC) ? 1 : 0);
-            geo_fma = (double)Q * (9 + 9 * Q);
-        }
-        double geo_mul = 0.0;
-        if (c->qlay == 1 && ho_geom_on(c)) {
-            // k_apply3d_tile<..., MF 32>: the same point operator with the tile's hoisting.  Per point 32 FMAs
-            // and 27 multiplications on top of the contractions at kinds 7: two columns of J from the column's
-            // hoisted parts (6 FMA), adj(J) (a mul and an FMA per entry; its first row alone without
-            // diffusion and convection), det J (1 mul, 2 FMA), W_q = (w_x w_y) w_z (1 mul); t, D, C, M as
-            // above.  Per column of points (thread), once: a1 + eta a4, a5 + eta a7, a2 + xi a4, a6 + xi a7
-            // (12 FMA), dx/dzeta (6 FMA), w_x w_y (1 mul).
-            const int na = g ? 9 : 3;
-            pt_fma = D * (1 + 3 * g) + D * (kD ? 4 : 1);
-            pt_mul = 0.0;
-            pt_fma += 6 + na + 2 + (g ? 6 : 0) + (kD ? 6 : 0) + (kC ? 2 : 0) + ((kM && kC) ? 1 : 0);
-            pt_mul += na + 1 + 1 + (g ? 3 : 0) + (kD ? 2 + 1 + 3 + 3 : 0) + (kC ? 2 : 0) + (kM ? 2 : 0) +
-                      ((kM && !kC) ? 1 : 0);
-            geo_fma = (double)Q * Q * 18;
-            geo_mul = (double)Q * Q;
-        }
-        const double fma = Q * ((double)D * D * D * (1 + g) + Q * ((double)D * D * (1 + 2 * g) + Q * pt_fma +
-                                                                   (double)D * D * (kD ? 3 : 1)) +
-                                (double)D * D * D * (kD ? 2 : 1)) + geo_fma;
-        const double mul = (double)Q * Q * Q * pt_mul + geo_mul;
-        *flops = (2.0 * fma + mul) * (double)c->ne;
+        *flops = kernel_flops(c, k);
         return CDFEM_OK;
     });
 }
@@ -2332,114 +1401,7 @@ int cdfem_kernel_bytes(cdfem_ctx *c, int k, double *bytes)
     return guarded(c, [&] {
         require_pa(c);
         if (!bytes) throw ArgError("bytes is null");
-        const double nl = (double)c->nl, ne = (double)c->ne, nd = c->nd;
-        if (k == CDFEM_K_UPDATE && c->last_method == CDFEM_BICGSTAB) {
-            // the five vector kernels of one BiCGStab iteration (bicgstab.hip): k_bcgs_p 4 N, k_bcgs_s 3 N,
-            // k_bcgs_x 7 N doubles; k_bcgs_v and k_bcgs_t each write their vector and read rh (s) and the
-            // diagonal when there is one (2 or 3 N), plus the apply's result: the output vector (N), or with
-            // the patch source the patch buffer, the essential flags and the apply's input on the essential
-            // rows (counted as the flags: the rows are few)
-            const double diag = c->bcgs_diag ? 1.0 : 0.0;
-            const double S = kBrick * c->p + 1.0;
-            const double src = c->bcgs_src ? 8.0 * S * S * S * (double)c->nblk + 1.0 * nl : 8.0 * nl;
-            *bytes = 8.0 * nl * (4 + 3 + 7) + 2.0 * (8.0 * nl * (2.0 + diag) + src);
-            return CDFEM_OK;
-        }
-        if (c->fa_ready) {  // CSR SpMV: values + columns + row pointers + x + y
-            if (k != CDFEM_K_APPLY) throw ArgError("FA operators report the SpMV (CDFEM_K_APPLY) only");
-            // (SELL adds < 1 % padding; 16-bit column deltas when the bandwidth fits)
-            // 8 B value + 2 B delta per entry (4 B column in the 32-bit slices of a mixed layout); LDS
-            // windows: 8 B value + 2 B window position per entry, 4 B per staged column (the x values
-            // themselves: 8 B per row, each window's halo beyond its own rows from L2)
-            if (c->lds_rows > 0)
-                *bytes = 10.0 * (double)c->nnz + 4.0 * (double)c->lds_halo + 4.0 * (double)(c->nslices + 1) +
-                         16.0 * nl;
-            else *bytes = spmv_delta(c) ? 10.0 * (double)c->nnz + 2.0 * (double)c->sell_nnz_wide + 4.0 * (nl + 1) + 16.0 * nl +
-                                         (c->d_swide ? (double)c->nslices : 0.0)
-                                   : 12.0 * (double)c->nnz + 4.0 * (nl + 1) + 16.0 * nl;
-            return CDFEM_OK;
-        }
-        const double nq = nq_of(c, c->rule_op);
-        if (use_hobrick_cg(c) && (k == CDFEM_K_APPLY || k == CDFEM_K_UPDATE)) {
-            // the high-order brick CG: factors + gathered r, M^-1, d + ess flags + d (writer) + patch
-            // outputs (+ x read and written under the x-fold); update: r, M^-1, ess, r write + patches
-            const double S = brick_patch_side(c), SZ = brick_patch_side_z(c);
-            const double patches = 8.0 * S * S * SZ * (double)brick_count(c);
-            const bool xf = c->cg_xfold != 0;
-            // (ho_uniform: one element matrix in operand order, 16 x 4 padded, instead of the factor stream)
-            const double nrow = 16.0 * ((c->nd + 15) / 16), ncol = 4.0 * ((c->nd + 3) / 4);
-            const double fac = ho_uniform_elem(c) ? 8.0 * nrow * ncol : 8.0 * c->ncomp * ne;
-            *bytes = k == CDFEM_K_APPLY ? fac + 33.0 * nl + patches + (xf ? 16.0 * nl : 0.0)
-                                        : (xf ? 25.0 : 49.0) * nl + patches;
-            return CDFEM_OK;
-        }
-        if (use_brick(c)) {
-            // CG-mode brick kernels (what the Krylov loop launches); see DESIGN.md section 4
-            const int64_t s1 = (int64_t)kBrick * c->p;
-            int64_t nface_dofs = 0;
-            for (int64_t z = 0; z < c->Lz; ++z)
-                for (int64_t y = 0; y < c->Ly; ++y) {
-                    if (z % s1 == 0 || y % s1 == 0) { nface_dofs += c->Lx; continue; }
-                    nface_dofs += (c->Lx - 1) / s1 + 1;
-                }
-            const double nf = (double)nface_dofs;
-            const double S = kBrick * c->p + 1.0;
-            const double patches = 8.0 * S * S * S * (double)c->nblk;  // the CG apply's patch outputs
-            // x-fold (cg_xfold, Kronecker form): x += alpha d moves from the update into the apply
-            const bool xf = c->cg_xfold != 0 && pa_af(c) == 2;
-            switch (k) {
-            case CDFEM_K_APPLY:   // qdata (or per-element affine factors) + gathered r, M^-1, d + ess
-                                  // flags + d (each dof by its one writer brick) + patch outputs
-                                  // (+ x read and written by its writer brick under the x-fold)
-                // (pa_uniform: one element matrix, 14 x 64 operand doubles, instead of the factor stream)
-                // (pa_geom: the element's mask and 21 map coefficients instead of its stream)
-                // (pa_uniform_diag: the 64-entry class table instead of the gathered M^-1)
-                *bytes = (uniform_elem(c) ? 8.0 * 14 * 64
-                          : pa_geom_on(c) ? 8.0 * GeomLayout::kNC * ne
-                                          : 8.0 * c->ncomp * (c->d_qaff ? 1.0 : nq) * ne) +
-                         (uniform_diag(c) ? 16.0 * nl + 8.0 * kUdiagN : 24.0 * nl) + 1.0 * nl + 8.0 * nl + patches +
-                         (xf ? 16.0 * nl : 0.0);
-                return CDFEM_OK;
-            case CDFEM_K_E2L:     // the Mult's row sums: the patch buffer + ess flags + y (brick_mult_pb,
-                                  // Kronecker form), or face partials + x, ess, y of the face dofs
-                *bytes = (c->brick_mult_pb && pa_af(c) == 2) ? patches + 9.0 * nl
-                                                             : 8.0 * c->nface * (double)c->nblk + 25.0 * nf;
-                return CDFEM_OK;
-            case CDFEM_K_UPDATE:  // x, d, r, M^-1 read, ess, x, r write + the patch outputs (each once);
-                                  // x-fold: r, M^-1, ess and r write only
-                // (pa_uniform_diag: no M^-1 stream; the essential flag it reads instead is counted above)
-                *bytes = (xf ? 25.0 : 49.0) * nl + patches - (uniform_diag(c) ? 8.0 * nl : 0.0);
-                return CDFEM_OK;
-            default: throw ArgError("kernel not launched on the brick path");
-            }
-        }
-        // the 3D applies on affine factors read one factor set per element (the 2D apply streams)
-        const double nqs = (c->qlay == 1 ? tile_affine(c) : (c->dim == 3 && c->d_qaff != nullptr)) ? 1.0 : nq;
-        // (ho_geom: the tile apply reads the element's 24 doubles of map coefficients instead of its stream)
-        const bool hgeo = c->qlay == 1 && ho_geom_on(c);
-        switch (k) {
-        case CDFEM_K_APPLY:
-            if (c->epencil)  // lattice gather: x + ess flags (each L-dof once) + qdata + E-vector write
-                *bytes = 9.0 * nl + (hgeo ? 8.0 * HoGeomLayout::kNC * ne : 8.0 * c->ncomp * nqs * ne) + 8.0 * nd * ne +
-                         (tile_dfold_ok(c) ? 16.0 * nl : 0.0);  // CG apply with the direction fold:
-                                                                // + d_old gather, + d store
-            else             // x gather (each L-dof once) + qdata stream + element map + E-vector write
-                             // (pa_geom: the element's mask and 21 map coefficients instead of its stream)
-                *bytes = 8.0 * nl + (c->qlay == 0 && c->dim == 3 && pa_geom_on(c) ? 8.0 * GeomLayout::kNC * ne
-                                     : hgeo                                       ? 8.0 * HoGeomLayout::kNC * ne
-                                                                                  : 8.0 * c->ncomp * nqs * ne) +
-                         4.0 * nd * ne + 8.0 * nd * ne;
-            break;
-        case CDFEM_K_E2L:
-            if (c->epencil)  // E-vector read + ess flags + y write + x read (constraint / dot)
-                *bytes = 8.0 * nd * ne + 1.0 * nl + 8.0 * nl + 8.0 * nl;
-            else             // E-vector read + positions + offsets + y write + x read (constraint / dot)
-                *bytes = 8.0 * nd * ne + 4.0 * nd * ne + 4.0 * nl + 8.0 * nl + 8.0 * nl;
-            break;
-        case CDFEM_K_UPDATE: *bytes = 8.0 * nl * 8; break;     // x,d,r,z,dinv read; x,r,z write
-        case CDFEM_K_DIRECTION: *bytes = 8.0 * nl * 3; break;  // z,d read; d write
-        default: throw ArgError("bad kernel id");
-        }
+        *bytes = kernel_bytes(c, k);
         return CDFEM_OK;
     });
 }

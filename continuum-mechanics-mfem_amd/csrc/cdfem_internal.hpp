@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/cdfem.h"
+#include "options.hpp"
 
 namespace cdfem {
 
@@ -136,7 +137,8 @@ struct ProfileSlot {
 
 }  // namespace cdfem
 
-struct cdfem_ctx {
+// the set_option switches and their defaults are the base (options.hpp); everything else is state
+struct cdfem_ctx : cdfem::Options {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
@@ -166,11 +168,8 @@ struct cdfem_ctx {
     // 3D p = 3, 4 on a structured box: blocks of kHoBrickEdge^3 elements for the high-order brick CG
     // (brick_kernels.hip k_hobrick_cg; set_option "ho_brick")
     int hb_nbx = 0, hb_nby = 0, hb_nbz = 0, hb_nblk = 0;
-    int ho_block_z = 2;                 // set_option "ho_block_z": elements per block along z (2 or 4), read by
-                                        // cdfem_mesh_set_structured; 4 = 2 x 2 x 4 blocks
     int hb_ez = 2;                      //   the block depth of the current structured box
     uint8_t *d_bess = nullptr;          // per brick (block): 1 if a dof of its patch is essential
-    int ho_brick = 1;                   // set_option "ho_brick": high-order CG through k_hobrick_cg + the brick update
     double *d_hbpart = nullptr;         // den partials summed in two stages: k_hobrick_cg's, and k_brick_cg's past
                                         // kDenFoldMaxParts bricks on one rank (one per brick)
     double *den_out = nullptr;          // k_brick_cg writes its den partials here instead of d_part (set by the solve)
@@ -178,28 +177,13 @@ struct cdfem_ctx {
     // GPU): the last-arriving brick of each group of den_grp sums the group's partials in a fixed order
     // (k_brick_cg tail: write-through partial, agent-scope arrival count), so the folds sum <= 4,096 values
     int den_grp = 1;                    // group size of the running solve (1: one partial per brick)
-    int den_group_opt = 0;              // set_option "den_group": 0 automatic, else this group size (tests)
     double *d_gsum = nullptr;           // [ceil(nblk / den_grp)] group sums
     uint32_t *d_gcnt = nullptr;         // [same] arrival counters (0 between launches)
     int64_t gsum_cap = 0;
-    int ho_brick_mfma = 0;              // set_option "ho_brick_mfma": its x stage on v_mfma_f64_16x16x4_f64 (kinds 7)
-    int brick_stagger = -1;             // set_option "brick_stagger": BrickGeom::stag (-1 automatic, 0 off)
-    int brick_mfma = 0;                 // set_option "brick_mfma": k_brick_cg's x stage on the matrix cores (p = 2, kinds 7)
-    int pa_uniform = 1;                 // set_option "pa_uniform": when every element's factors equal the first
-                                        // element's (a uniformly refined box, what MFEM's MakeCartesian3D
-                                        // gives), the p = 2 brick CG applies that element's 27 x 27 matrix on
-                                        // the matrix cores (brick_um.hip k_brick_cg<XF, BF, FULL>); 0 keeps the Kronecker form
     double *d_uelem = nullptr;          // pa_uniform: the common element matrix in MFMA A-operand order
-    int pa_uniform_diag = 1;            // set_option "pa_uniform_diag": with pa_uniform, the Jacobi-CG apply and update take
-                                        // M^-1 from the 64 lattice-class values of d_udiag instead of streaming d_dinv
     double *d_udiag = nullptr;          // [kUdiagN] the class table (setup_uniform_diag, valid while dinv_ready;
                                         // null when the device check found d_dinv not class-constant)
     bool udiag_bitwise = false;         //   every non-essential entry of d_dinv equals its class entry bitwise
-    int ho_uniform = 0;                 // set_option "ho_uniform": the p = 3, 4 block CG (2 x 2 x 4 blocks) applies the
-                                        // common N x N element matrix of a uniform box (N = 64, 125) as one GEMM on
-                                        // the matrix cores (k_hobrick_um); read by cdfem_pa_setup, 0 afterwards
-                                        // switches back to the Kronecker form without a new setup
-    int ho_uniform_grid = 0;            // set_option "ho_uniform_grid": k_hobrick_um's workgroups (0 automatic; tests)
     double *d_hoelem = nullptr;         // ho_uniform: that matrix in MFMA A-operand order ([row tile][k step][lane],
                                         // zero-padded to 16 x 4 multiples: 128 x 128 at p = 4)
     int hoelem_p = 0;                   //   the order and kinds it was formed for
@@ -209,17 +193,8 @@ struct cdfem_ctx {
     double *d_ones = nullptr;           // all-ones vector (unpreconditioned brick CG)
     double *d_dalt = nullptr;           // second search-direction buffer (brick CG)
     int nface = 0;                      // F
-    int gm_ept = 0;                     // set_option "gm_ept": GMRES orthogonalisation entries per thread (0: auto, orth_ept)
     int gm_ept_auto = 4;                // the automatic choice for vectors of gm_ept_n entries
-    int gm_pb = 1;                      // set_option "gm_pb": GMRES pass 1 reads the structured Mult's patch buffer
-    int gm_poll = 4;                    // set_option "gm_poll": the host polls the GMRES state every k inner steps
     int64_t gm_ept_n = -1;
-    int brick_xcd = 1;                  // k_brick_cg brick order: 0 dispatch, 1 XCD-contiguous (default)
-    // the brick kernels address r, M^-1, d, x, ess and the patch buffer through buffer resources with
-    // 32-bit byte offsets and the out-of-range marker kOOB = 2^31, so every such buffer must stay below
-    // 2^31 bytes (8 N_L and 8 S^3 nblk); larger boxes take the generic 64-bit-indexed element kernels.
-    // set_option "brick_byte_limit" lowers the bound (tests force the fallback on small boxes).
-    int64_t brick_limit = (int64_t)1 << 31;
     // slab partition: the largest L-vector and brick count over all ranks (all-reduced by cdfem_set_slab),
     // so brick_fits takes the same decision on every rank (slabs of different sizes near the
     // bound would otherwise send ranks down CG paths with different collective sequences)
@@ -280,35 +255,16 @@ struct cdfem_ctx {
     int16_t *d_sdel = nullptr;          // 16-bit column deltas (null when the bandwidth does not fit)
     uint8_t *d_swide = nullptr;         // per slice: 1 = streams 32-bit columns (mixed layout; null: none)
     int64_t sell_nnz_wide = 0;          // real entries in the 32-bit slices of a mixed layout
-    int mr_overlap = 1;                 // set_option "mr_overlap": slab CG exchange overlapped with interior bricks
     hipStream_t stream2 = nullptr;      // side stream of the overlapped exchange (created on first use)
     hipEvent_t ov_ev[2] = {};           // fork / join of the side stream
-    int brick_mult_pb = 1;              // set_option "brick_mult_pb": structured Mult through the patch buffer
-    int cg_beta_fold = 1;               // set_option "cg_beta_fold": brick CG betanom step in the next apply
-    int cg_beta_sum = 0;                // set_option "cg_beta_sum": with it, on one rank before the uniform-box apply, the
-                                        // update's last workgroup sums the betanom partials once (cg_beta_sum_on);
-                                        // off: measured slower (profiles/r14/ab_c2_one_round/)
-    double *d_bsum = nullptr;           // [2] that sum, then the update's arrival counter (0 between launches)
-    int cg_mr_fold = 1;                 // set_option "cg_mr_fold": both folds on several ranks (partials all-reduced)
+    double *d_bsum = nullptr;           // [2] cg_beta_sum: the betanom sum, then the update's arrival counter (0 between launches)
     double *d_small = nullptr;          // a few doubles of device scratch (mr_fold_agreed's all-reduce)
-    int cg_den_fold = 1024;             // set_option "cg_den_fold": brick CG den step in the update (N workgroups; 0 off)
-    int brick_upd_pb = 1;               // set_option "brick_upd_pb": predicated-load face sums in the brick CG update
-    int ho_dfold = 1;                   // set_option "ho_dfold": CG direction folded into the Kronecker tile apply
-    int ho_mfma = 0;                    // set_option "ho_mfma": bit 0 = stage x of the p >= 3 tile apply on MFMA
-    int cg_fused = 1;                   // set_option "cg_fused": fused high-order CG iteration (p >= 3 boxes)
-    int cg_xfold = 1;                   // set_option "cg_xfold": brick CG folds x += alpha d into the next apply
-    int spmv_index16 = 1;               // set_option "spmv_index16": SpMV streams d_sdel when present
-    int sell_mode = 8;                  // set_option "sell_order" (read when the FA pattern is built)
-    int sell_window = 0;                // set_option "sell_window": rows per window of a windowed order (0 auto)
-    int spmv_lds = -1;                  // set_option "spmv_lds": rows per LDS-staged SpMV window (0 off, -1 auto)
     int32_t *d_hptr = nullptr, *d_hidx = nullptr;  // LDS-staged windows (FaPattern::hptr / hidx / sloc)
     uint16_t *d_sloc = nullptr;
     int64_t lds_rows = 0;               // rows per window of the current LDS layout (0: none)
     int32_t lds_max = 0;                // largest window halo (doubles)
     int64_t lds_halo = 0;               // staged columns over all windows
-    int spmv_lpr = 0;                   // set_option "spmv_lpr": lanes per row of the LDS layouts (0 auto, 1, 2, 4)
     int sell_lpr = 1;                   // lanes per row of the current SELL copy
-    int spmv_xcd = 1;                   // set_option "spmv_xcd": contiguous slice range per XCD (windowed layout)
     int32_t *d_rperm = nullptr;         // SpMV space order: space row -> mesh row (null: mesh order)
     bool sell_windowed = false;         // slices cut from the space order (kernel row = slice * 64 + lane)
     double *d_pv[2] = {};               // permuted-space scratch (apply in mesh order; solve B / X)
@@ -324,17 +280,7 @@ struct cdfem_ctx {
     double *d_qd = nullptr;             // [nblk][nq][nc][64]
     double *d_qaff = nullptr;           // [nblk][nc][64] per-element factors of an affine mesh (qd = W_q * g)
     bool mesh_affine = false;           // every element a parallelepiped (checked at upload)
-    int pa_affine = 2;                  // set_option "pa_affine": when the mesh allows, 1 form the point data
-                                        // from the affine factors, 2 the Kronecker form of the same factors
-                                        // (3D p <= 2 applies; the p >= 3 tile apply takes 2 as 1); 0 stream
-    int pa_geom = 0;                    // set_option "pa_geom": 1 = on a hex mesh the affine forms do not take (3D
-                                        // p <= 2, constant coefficients) the applies form the point data from the
-                                        // element's trilinear map (AF 3) instead of streaming it; read by
-                                        // cdfem_pa_setup, 0 afterwards switches back to the stream
     double *d_geom = nullptr;           // pa_geom: header + [nblk][22][64] masks and map coefficients (GeomLayout)
-    int ho_geom = 0;                    // set_option "ho_geom": the same for the 3D p = 3, 4 tile apply where it runs
-                                        // the stream (MF & 32 of k_apply3d_tile); read by cdfem_pa_setup, 0
-                                        // afterwards switches back to the stream
     double *d_hgeom = nullptr;          // ho_geom: GeomLayout's header + [ne][24] map coefficients (HoGeomLayout)
     double *d_Ye = nullptr;             // [nblk][nd][64]
     double *d_dinv = nullptr;           // Jacobi (constrained: ess -> 1)
@@ -369,7 +315,6 @@ struct cdfem_ctx {
     // profiling
     bool profile = false;
     cdfem::ProfileSlot prof[CDFEM_K_COUNT];
-    unsigned prof_mask = ~0u;  // kernels that get HIP events while profiling (set_option profile_mask)
     hipEvent_t ext_ev[2] = {};  // armed by prof_mark(begin): the next CDFEM_LAUNCH records these
                                 // events at its own dispatch start / end (hipExtLaunchKernelGGL)
 };
@@ -664,5 +609,19 @@ void ilu_free(cdfem_ctx *c);
 hipError_t ilu_apply(cdfem_ctx *c);
 // f64 compute-rate probes: mode 0 VALU v_fma_f64, 1 v_mfma_f64_16x16x4_f64; *flops per launch
 hipError_t launch_fp64_probe(cdfem_ctx *c, int mode, double *out, double *flops);
+
+// ---- the operator and the Krylov drivers (solve.hip), the cost model (model.hip) ----------------
+bool use_brick(const cdfem_ctx *c);       // the p <= 2 brick kernels run the structured Mult and CG
+bool use_hobrick_cg(const cdfem_ctx *c);  // the p = 3, 4 block CG runs
+bool use_brick_cg(const cdfem_ctx *c);    // either
+void op_apply(cdfem_ctx *c, const double *x, double *y, bool constrained);         // rank-local
+void op_apply_global(cdfem_ctx *c, const double *x, double *y, bool constrained);  // + shared dofs summed
+void ensure_dinv(cdfem_ctx *c);           // d_dinv (and the pa_uniform_diag table) formed once per operator
+// the Krylov driver p.method and the context select; dB, dX on the device, in the solve's order
+void solve(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, double *dX, cdfem_solver_result &res);
+inline int nq_of(const cdfem_ctx *c, const Rule1D &r) { return c->dim == 3 ? r.q1 * r.q1 * r.q1 : r.q1 * r.q1; }
+void kernel_name(const cdfem_ctx *c, int k, char *buf, size_t n);
+double kernel_flops(const cdfem_ctx *c, int k);
+double kernel_bytes(const cdfem_ctx *c, int k);
 
 }  // namespace cdfem

@@ -95,16 +95,28 @@ def test_rccl_selftest_built_against_rccl():
 
 
 def test_every_option_key_is_documented():
-    """Every key cdfem_set_option accepts (capi.hip) is documented with its default in
-    include/cdfem.h, and an unknown key is refused (no silent no-op switches)."""
+    """Every key cdfem_set_option accepts (the rows of the table in options.hpp) is documented with
+    its default in include/cdfem.h, the keys are the 36 of the else-if ladder the table replaced, and an
+    unknown key is refused (no silent no-op switches)."""
     import os
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "continuum-mechanics-mfem_amd", "csrc", "capi.hip")).read()
+    src = open(os.path.join(root, "continuum-mechanics-mfem_amd", "csrc", "options.hpp")).read()
     hdr = open(os.path.join(root, "include", "cdfem.h")).read()
-    keys = sorted(set(re.findall(r'k == "([a-z_0-9]+)"', src)))
+    table = src[src.index("kOptionTable[] = {"):]
+    table = table[:table.index("\n};")]
+    rows = re.findall(r'^    \{"([a-z_0-9]+)",', table, flags=re.M)
+    keys = sorted(set(rows))
+    assert len(rows) == len(keys), "a key has two rows"
     assert len(keys) >= 8
     missing = [k for k in keys if f'"{k}"' not in hdr]
     assert not missing, missing
-    # refusal of an unknown key needs a context, i.e. a GPU: pinned by the source instead
+    assert keys == sorted("""
+        brick_xcd brick_byte_limit den_group cg_mr_fold ho_brick_mfma brick_stagger pa_uniform pa_uniform_diag
+        ho_uniform ho_uniform_grid brick_mfma ho_block_z ho_brick mr_overlap brick_mult_pb cg_beta_fold cg_beta_sum
+        cg_den_fold brick_upd_pb ho_dfold ho_mfma cg_xfold cg_fused sell_order gm_poll gm_pb pa_affine pa_geom
+        ho_geom spmv_lpr spmv_lds sell_window gm_ept spmv_xcd spmv_index16 profile_mask""".split())
+    assert len(keys) == 36
+    # refusal of an unknown key needs a context, i.e. a GPU (tests/test_gpu_options.py); the text is pinned
+    # by the source here and checked by tests/cpp/options_check.cpp
     assert 'unknown option' in src
