@@ -1,13 +1,28 @@
-// brick_core.hpp — the structured-box lattice geometry, raw buffer access and the patch-buffer row
-// sum, shared by the brick kernels (brick_kernels.hip) and the GMRES passes that read the structured
-// Mult's patch buffer directly (gmres.hip).
+// brick_core.hpp — the brick CG apply protocol and the lattice geometry, raw buffer access and patch-buffer
+// row sum (patch_sum8) that the brick kernels, the update kernel and the GMRES / BiCGStab passes share.
+// The protocol of an apply brick (k_brick_cg of brick_um.hip and of brick_kernels.hip at p <= 2, k_hobrick_cg
+// and k_hobrick_um on the p = 3, 4 blocks), and its pieces here:
+//   - its place in the lattice: brick_id (XCD order: xcd_order, brick_lattice.hpp), brick_pos -> BrickPos;
+//   - the patch gather and d = M^-1 r + beta d_old, stored by the dof's writer brick (is_writer) with the x-fold
+//     (each kernel's own loops: they differ in layout and register parking on purpose);
+//   - at p = 2, where enabled, the previous update's betanom step (beta_fold);
+//   - the element operator (each kernel's own);
+//   - the whole patch -> the patch buffer in the pencil layout (patch_store);
+//   - the den partial (den_publish, with the grouped tail).
+// Both k_brick_cg kernels take brick_pos, is_writer, beta_fold and den_publish; the uniform-box one and
+// k_brick3d<PBO> also patch_store.  k_hobrick_cg takes is_writer; otherwise the block kernels still carry
+// their own text of steps 1 and 3: which helper costs registers or time at which site is on record in
+// profiles/r16/brick_protocol/.  A dof's 1-8 patch entries are summed in one order everywhere (brick_holders
+// of brick_lattice.hpp, patch_sum8), which makes the branchy and predicated-load sums bitwise equal.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <type_traits>
 
+#include "brick_lattice.hpp"
 #include "pa_core.hpp"
+#include "reduce.hpp"
 
 #ifndef CDFEM_PS8_SKIP
 #define CDFEM_PS8_SKIP 1
@@ -89,15 +104,38 @@ struct PatchWalk {
     }
 };
 
-// workgroup b runs on XCD b % 8; with xcd = 1 each XCD takes a contiguous range of bricks, so a
-// brick's neighbours (which re-read its patch faces) are mostly on the same L2.  Measured in
-// process (tools/ab.py, 64^3 p=2, two boxes): 242.8 vs 258.6 us per k_brick_cg launch; at 256^3
-// no difference (14444 vs 14470 us).
+// the launch-local brick of this workgroup: with xcd = 1 in xcd_order.  Measured in process (tools/ab.py,
+// 64^3 p=2, two boxes): 242.8 vs 258.6 us per k_brick_cg launch; at 256^3 no difference (14444 vs 14470 us).
 __device__ __forceinline__ int brick_id(const BrickGeom &g)
 {
     if (!g.xcd) return blockIdx.x;
-    const unsigned G = gridDim.x, b = blockIdx.x, x = b % 8, k = b / 8, q = G / 8, r = G % 8;
-    return (int)(x * q + (x < r ? x : r) + k);
+    const unsigned G = gridDim.x, b = blockIdx.x;
+    return xcd_order(b, G);
+}
+
+// Launch-local brick bl -> the global brick b (a launch covers every g.bzs-th layer from g.bz0), its place
+// (bx, by, bz) in the brick grid, the lattice origin of its S x S x SZ patch, and whether it is the last brick
+// of an axis (which then also writes the dofs of its upper patch face)
+struct BrickPos {
+    int b, bx, by, bz, gx0, gy0, gz0;
+    bool lastx, lasty, lastz;
+};
+template <int S, int SZ = S>
+__device__ __forceinline__ BrickPos brick_pos(const BrickGeom &g, int bl)
+{
+    const int nxy = g.nbx * g.nby;
+    const int bz = g.bz0 + (bl / nxy) * g.bzs;
+    const int b = bl % nxy + nxy * bz;
+    const int bx = b % g.nbx, by = (b / g.nbx) % g.nby;
+    return BrickPos{b, bx, by, bz, (S - 1) * bx, (S - 1) * by, (SZ - 1) * bz,
+                    bx == g.nbx - 1, by == g.nby - 1, bz == g.nbz - 1};
+}
+// every lattice dof has exactly one writer brick: the one holding it below its upper patch faces (in: the
+// position lies inside the lattice)
+template <int S, int SZ = S>
+__device__ __forceinline__ bool is_writer(int px, int py, int pz, bool in, const BrickPos &p)
+{
+    return in && (px < S - 1 || p.lastx) && (py < S - 1 || p.lasty) && (pz < SZ - 1 || p.lastz);
 }
 
 // PatchWalk plus the lattice index gid = gx + Lx gy + Lxy gz of the position, advanced with the walk's
@@ -149,6 +187,88 @@ __device__ __forceinline__ int opaque(int v)
 {
     asm volatile("" : "+v"(v));
     return v;
+}
+
+// A brick's patch -> the patch buffer pb ([bz][pz][by][py][bx][px], patch_idx in 32-bit arithmetic with the
+// brick's part uniform: index = base + pz A + py R + px).  Thread tid of NT stores positions i = tid, tid + NT,
+// ... (NI of them, the last only while i < S S SZ) with the entries val(k, i, px, py, pz); what an entry is stays
+// in the kernel.  (tid is made opaque: the walk's index arithmetic stays below the element apply.)
+template <int S, int SZ = S, int NT = 64, typename F>
+__device__ __forceinline__ void patch_store(double *pb, const BrickGeom &g, int bx, int by, int bz, int tid, F &&val)
+{
+    constexpr int S3 = S * S * SZ, NI = (S3 + NT - 1) / NT;
+    const uint32_t R = (uint32_t)g.nbx * S, A = (uint32_t)g.nby * S * R;
+    const uint32_t base = (uint32_t)bz * SZ * A + (uint32_t)by * S * R + (uint32_t)bx * S;
+    const auto bp = brsrc(pb, 8u * (uint32_t)g.nbx * g.nby * g.nbz * S3);
+    const unsigned to = (unsigned)opaque(tid);
+    PatchWalk<S, NT> pw(to);
+#pragma unroll
+    for (int k = 0; k < NI; ++k) {
+        const unsigned i = to + NT * k;
+        if (k == NI - 1 && i >= S3) break;
+        bstore(bp, 8u * (base + (uint32_t)pw.z * A + (uint32_t)pw.y * R + (uint32_t)pw.x), val(k, i, pw.x, pw.y, pw.z));
+        pw.next();
+    }
+}
+
+// The den partial of brick b (one wave; t its lane): part[b], and with grouped partials (grp = den_grp > 1)
+// the group's sum.  The partial goes out write-through (sc1: an agent-scope relaxed store), the wave waits for
+// it, then counts its arrival on the group's agent-scope counter; the brick whose add returns the group's last
+// count reads the group's partials with sc1 loads (L2 and L1 bypassed: correct wherever the group's bricks
+// ran, MI355X_MICROARCH.md inter-workgroup visibility) and sums them by the fixed wave tree, so the group sum
+// does not depend on the order of arrival.  The counter is reset for the next launch by the same brick.
+__device__ __forceinline__ void den_publish(double den, int t, int b, double *part, double *gsum, uint32_t *gcnt,
+                                            int grp, int nbrick)
+{
+    den = wave_sum(den);
+    if (grp <= 1) {
+        if (t == 0) part[b] = den;
+        return;
+    }
+    const int gi = b / grp, g0 = gi * grp, gn = min(grp, nbrick - g0);
+    uint32_t prev = 0;
+    if (t == 0) {
+        __hip_atomic_store(&part[b], den, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        prev = __hip_atomic_fetch_add(&gcnt[gi], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    prev = (uint32_t)__shfl((int)prev, 0, 64);
+    if (prev != (uint32_t)(gn - 1)) return;
+    double v = t < gn ? __hip_atomic_load(&part[g0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+    v = wave_sum(v);
+    if (t == 0) {
+        gsum[gi] = v;
+        __hip_atomic_store(&gcnt[gi], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// The betanom step of the previous update, taken by the p = 2 apply after kk updates (set_option
+// "cg_beta_fold"): betanom from the update's partials pv, which the kernel loaded ahead of its gather (BF 1:
+// lane t holds partials t, t + 64, ..., summed in this one order; BF 2: pv[0] is the sum the update's last
+// workgroup left), cg_update_logic's decision (cg_stop_kind) taken identically by every workgroup at the
+// host's update count kk and recorded by global brick 0 (one launch records, also when a slab is split in
+// two), and beta.  True: the solve stops here.
+template <int BF, int N>
+__device__ __forceinline__ bool beta_fold(const double (&pv)[N], KrylovState *st, int kk, int b, int t, double &beta)
+{
+    if (kk <= 0) return false;
+    double B = pv[0];
+    if constexpr (BF == 1) {
+        double v = 0.0;
+#pragma unroll
+        for (int q = 0; q < N; ++q) v += pv[q];
+        B = wave_sum(v);
+    }
+    const bool stop = cg_stop_kind(st, B, kk) != kCgGoOn;
+    if (b == 0 && t == 0) {
+#ifdef CDFEM_DEBUG
+        assert(st->iter == kk);
+#endif
+        cg_update_logic_at(st, B, kk);
+    }
+    if (stop) return true;
+    beta = B / st->nom;
+    return false;
 }
 
 // The 1-8 patch-buffer entries of lattice dof (gx, gy, gz) summed in a fixed order (lower brick first

@@ -174,20 +174,9 @@ k_brick3d(const double *__restrict__ x, double *__restrict__ y, double *__restri
     brick_e2l<D1, S>(s_out, o0, Y);
 
     if constexpr (PBO) {
-        // 4'. the whole patch -> the patch buffer (32-bit index: base + pz A + py R + px)
-        const uint32_t R = (uint32_t)g.nbx * S, A = (uint32_t)g.nby * S * R;
-        const int bxp = b % g.nbx, byp = (b / g.nbx) % g.nby, bzp = b / (g.nbx * g.nby);
-        const uint32_t base = (uint32_t)bzp * S * A + (uint32_t)byp * S * R + (uint32_t)bxp * S;
-        const auto bp = brsrc(face, 8u * (uint32_t)g.nbx * g.nby * g.nbz * S3);
-        const unsigned tp = (unsigned)opaque(t);
-        PatchWalk<S> pw(tp);
-#pragma unroll
-        for (int k = 0; k < NI; ++k) {
-            const unsigned i = tp + 64 * k;
-            if (k == NI - 1 && i >= S3) break;
-            bstore(bp, 8u * (base + (uint32_t)pw.z * A + (uint32_t)pw.y * R + (uint32_t)pw.x), s_out[i]);
-            pw.next();
-        }
+        // 4'. the whole patch -> the patch buffer (patch_store)
+        patch_store<S>(face, g, b % g.nbx, (b / g.nbx) % g.nby, b / (g.nbx * g.nby), t,
+                       [&](int, unsigned i, int, int, int) { return s_out[i]; });
         return;
     }
     // 4. owned dofs -> y (constrained: y = x on ess rows), face dofs -> this brick's partials
@@ -223,36 +212,20 @@ k_brick3d(const double *__restrict__ x, double *__restrict__ y, double *__restri
 // Sum the brick-face partials of every dof lying on a brick face: one thread per face dof.
 // Grid (x, z-plane): a plane gz = multiple of 4p is all face dofs; any other plane holds full
 // lines (gy = multiple of 4p) and, on the remaining lines, the dofs gx = 0, 4p, 8p, ...
-// CG mode also forms d = M^{-1} r + beta d for these dofs and the partial (d, A d).
+// MODE as k_brick3d's.
 template <int S, int MODE>
 __global__ void __launch_bounds__(kRedThreads)
-k_brick_faces(const double *__restrict__ x, const double *__restrict__ dinv, double *__restrict__ d,
-              double *__restrict__ y, const double *__restrict__ face, const uint8_t *__restrict__ ess,
-              const BrickGeom g, double *__restrict__ part, const KrylovState *__restrict__ st)
+k_brick_faces(const double *__restrict__ x, double *__restrict__ y, const double *__restrict__ face,
+              const uint8_t *__restrict__ ess, const BrickGeom g)
 {
     constexpr int F = face_count<S>();
     constexpr int s1 = S - 1;
-    __shared__ double sh[kRedThreads / 64];
-    double beta = 0.0;
-    if constexpr (MODE == 2) {
-        if (st->done) return;
-        beta = st->beta;
-    }
     const int gz = blockIdx.y;
     const bool fz = gz % s1 == 0;
     const int Lx = g.Lx, Ly = g.Ly;
     const int nfx = (Lx - 1) / s1 + 1, nfy = (Ly - 1) / s1 + 1;
     const int per = Lx + (s1 - 1) * nfx;                     // dofs per s1-line period (sparse plane)
     const int count = fz ? Lx * Ly : nfy * Lx + (Ly - nfy) * nfx;
-    int bzs[2], pzs[2], nzc = 0;
-    {
-        const int qz = gz / s1;
-        if (fz) {
-            if (qz - 1 >= 0) { bzs[nzc] = qz - 1; pzs[nzc] = s1; ++nzc; }
-            if (qz < g.nbz) { bzs[nzc] = qz; pzs[nzc] = 0; ++nzc; }
-        } else { bzs[0] = qz; pzs[0] = gz - qz * s1; nzc = 1; }
-    }
-    double acc = 0.0;
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
         int gx, gy;
         if (fz) {
@@ -262,41 +235,13 @@ k_brick_faces(const double *__restrict__ x, const double *__restrict__ dinv, dou
             if (rem < Lx) { gy = s1 * pi; gx = rem; }
             else { const int j = rem - Lx, jl = j / nfx; gy = s1 * pi + 1 + jl; gx = (j - jl * nfx) * s1; }
         }
-        int bxs[2], pxs[2], nxc = 0, bys[2], pys[2], nyc = 0;
-        {
-            const int qx = gx / s1, qy = gy / s1;
-            if (gx - qx * s1 == 0) {
-                if (qx - 1 >= 0) { bxs[nxc] = qx - 1; pxs[nxc] = s1; ++nxc; }
-                if (qx < g.nbx) { bxs[nxc] = qx; pxs[nxc] = 0; ++nxc; }
-            } else { bxs[0] = qx; pxs[0] = gx - qx * s1; nxc = 1; }
-            if (gy - qy * s1 == 0) {
-                if (qy - 1 >= 0) { bys[nyc] = qy - 1; pys[nyc] = s1; ++nyc; }
-                if (qy < g.nby) { bys[nyc] = qy; pys[nyc] = 0; ++nyc; }
-            } else { bys[0] = qy; pys[0] = gy - qy * s1; nyc = 1; }
-        }
         double sum = 0.0;
-        for (int kz = 0; kz < nzc; ++kz)
-            for (int ky = 0; ky < nyc; ++ky)
-                for (int kx = 0; kx < nxc; ++kx) {
-                    const int bb = bxs[kx] + g.nbx * (bys[ky] + g.nby * bzs[kz]);
-                    sum += face[(size_t)bb * F + face_index<S>(pxs[kx], pys[ky], pzs[kz])];
-                }
+        brick_holders<S>(g.nbx, g.nby, g.nbz, gx, gy, gz, [&](int bx, int by, int bz, int px, int py, int pz) {
+            sum += face[(size_t)(bx + g.nbx * (by + g.nby * bz)) * F + face_index<S>(px, py, pz)];
+        });
         const int64_t gid = gx + (int64_t)Lx * (gy + (int64_t)Ly * gz);
-        if constexpr (MODE == 0) {
-            y[gid] = sum;
-        } else if constexpr (MODE == 1) {
-            y[gid] = ess[gid] ? x[gid] : sum;
-        } else {
-            const double dn = dinv[gid] * x[gid] + beta * d[gid];
-            d[gid] = dn;
-            const double q = ess[gid] ? dn : sum;
-            y[gid] = q;
-            acc += dn * q;
-        }
-    }
-    if constexpr (MODE == 2) {
-        const double bs = block_sum(acc, sh);
-        if (threadIdx.x == 0) part[blockIdx.x + gridDim.x * blockIdx.y] = bs;
+        if constexpr (MODE == 0) y[gid] = sum;
+        else y[gid] = ess[gid] ? x[gid] : sum;
     }
 }
 
@@ -383,8 +328,7 @@ static dim3 faces_grid(const cdfem_ctx *c)
 }
 
 template <int D1, int Q1, unsigned K, int MODE>
-static hipError_t brick_launch(cdfem_ctx *c, const double *x, const double *dinv, double *d, double *y,
-                               int which)
+static hipError_t brick_launch(cdfem_ctx *c, const double *x, double *y, int which)
 {
     constexpr int S = kBrick * (D1 - 1) + 1;
     const BrickGeom g = geom_of(c);
@@ -415,8 +359,7 @@ static hipError_t brick_launch(cdfem_ctx *c, const double *x, const double *dinv
     }
     if (which & 2) {
         const dim3 fg = faces_grid(c);
-        hipLaunchKernelGGL((k_brick_faces<S, MODE>), fg, dim3(kRedThreads), 0, c->stream, x, dinv, d, y,
-                           c->d_face, c->d_ess, g, c->d_part + c->nblk, c->d_state);
+        hipLaunchKernelGGL((k_brick_faces<S, MODE>), fg, dim3(kRedThreads), 0, c->stream, x, y, c->d_face, c->d_ess, g);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -424,21 +367,19 @@ static hipError_t brick_launch(cdfem_ctx *c, const double *x, const double *dinv
 }
 
 template <int MODE>
-static hipError_t brick_dispatch(cdfem_ctx *c, const double *x, const double *dinv, double *d, double *y,
-                                 int which)
+static hipError_t brick_dispatch(cdfem_ctx *c, const double *x, double *y, int which)
 {
     if (c->rule_op.q1 != c->p + 2) return hipErrorInvalidValue;
     return dispatch_value<1, 2>(c->p, hipErrorInvalidValue, [&](auto P) {
         return dispatch_kinds(c->kinds, hipErrorInvalidValue, [&](auto K) {
-            return brick_launch<P() + 1, P() + 2, K(), MODE>(c, x, dinv, d, y, which);
+            return brick_launch<P() + 1, P() + 2, K(), MODE>(c, x, y, which);
         });
     });
 }
 
 hipError_t launch_brick_mult(cdfem_ctx *c, const double *x, double *y, bool constrained, int which)
 {
-    return constrained ? brick_dispatch<1>(c, x, nullptr, nullptr, y, which)
-                       : brick_dispatch<0>(c, x, nullptr, nullptr, y, which);
+    return constrained ? brick_dispatch<1>(c, x, y, which) : brick_dispatch<0>(c, x, y, which);
 }
 
 // ================================================================================================
@@ -523,13 +464,8 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv,
     // a run-time one costs every position's writer mask a scalar register pair.
     const double alpha_prev = XF ? st->alpha : 0.0;
     const int t = threadIdx.x;
-    // launch-local brick -> global brick (a launch covers every g.bzs-th layer from g.bz0)
-    const int bl = brick_id(g), nxy = g.nbx * g.nby;
-    const int bz = g.bz0 + (bl / nxy) * g.bzs;
-    const int b = bl % nxy + nxy * bz;
-    const int bx = b % g.nbx, by = (b / g.nbx) % g.nby;
-    const int gx0 = (S - 1) * bx, gy0 = (S - 1) * by, gz0 = (S - 1) * bz;
-    const bool lastx = bx == g.nbx - 1, lasty = by == g.nby - 1, lastz = bz == g.nbz - 1;
+    const BrickPos pos = brick_pos<S>(g, brick_id(g));
+    const int b = pos.b, bx = pos.bx, by = pos.by, bz = pos.bz, gx0 = pos.gx0, gy0 = pos.gy0, gz0 = pos.gz0;
     const double *q0 = qd_block<Q1, K, AF>(qd, b);  // AF: per-element factors (3: geometry, pa_geom)
     double den = 0.0;
     // patch gather: every load of the patch is issued before any is consumed (clamped indices,
@@ -580,7 +516,7 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv,
         mv[k] = bload(bm, off);
         ov[k] = bload(bo, off);
         ev[k] = __builtin_amdgcn_raw_buffer_load_b8(be, in ? gid : kOOB, 0, 0);
-        const bool writer = in && (px < S - 1 || lastx) && (py < S - 1 || lasty) && (pz < S - 1 || lastz);
+        const bool writer = is_writer<S>(px, py, pz, in, pos);
         woffv[k] = writer ? off : kOOB;
         dbits |= (uint32_t)(writer && !(zlo_shared && gz == 0)) << k;
         if constexpr (XF) xv[k] = bload(bxf, woffv[k]);
@@ -606,23 +542,7 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv,
     };
     static_for<0, GK>(gather);
     if constexpr (BF) {
-        if (kk > 0) {
-            double v = 0.0;
-#pragma unroll
-            for (int q = 0; q < NPL; ++q) v += pv[q];
-            const double B = wave_sum(v);
-            // cg_update_logic's decision (cg_stop_kind), taken identically by every workgroup at the
-            // host's update count kk; workgroup 0 records it at the same kk
-            const bool stop = cg_stop_kind(st, B, kk) != kCgGoOn;
-            if (b == 0 && t == 0) {  // (global brick 0: one launch records, also when a slab is split in two)
-#ifdef CDFEM_DEBUG
-                assert(st->iter == kk);
-#endif
-                cg_update_logic_at(st, B, kk);
-            }
-            if (stop) return;
-            beta = B / st->nom;
-        }
+        if (beta_fold<1>(pv, st, kk, b, t, beta)) return;
     }
     static_for<0, GK>(form);
     if constexpr (NG == 2) {
@@ -725,32 +645,7 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv,
             pw.next();
         }
     }
-    den = wave_sum(den);
-    if (grp <= 1) {
-        if (t == 0) part[b] = den;
-        return;
-    }
-    // grouped partials (den_grp > 1): the partial goes out write-through (sc1: an agent-scope relaxed
-    // store), the wave waits for it, then counts its arrival on the group's agent-scope counter; the
-    // brick whose add returns the group's last count reads the group's partials with sc1 loads (L2 and
-    // L1 bypassed: correct wherever the group's bricks ran, MI355X_MICROARCH.md inter-workgroup
-    // visibility) and sums them by the fixed wave tree, so the group sum does not depend on the order
-    // of arrival.  The counter is reset for the next launch by the same brick.
-    const int gi = b / grp, g0 = gi * grp, gn = min(grp, nbrick - g0);
-    uint32_t prev = 0;
-    if (t == 0) {
-        __hip_atomic_store(&part[b], den, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        prev = __hip_atomic_fetch_add(&gcnt[gi], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    prev = (uint32_t)__shfl((int)prev, 0, 64);
-    if (prev != (uint32_t)(gn - 1)) return;
-    double v = t < gn ? __hip_atomic_load(&part[g0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-    v = wave_sum(v);
-    if (t == 0) {
-        gsum[gi] = v;
-        __hip_atomic_store(&gcnt[gi], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    den_publish(den, t, b, part, gsum, gcnt, grp, nbrick);
 }
 
 // PB (set_option "brick_upd_pb"): the 1-8 patch entries of every dof as eight unconditional buffer
@@ -777,7 +672,6 @@ k_cg_update_faces(double *__restrict__ x, double *__restrict__ r, const double *
                   double *__restrict__ part, KrylovState *__restrict__ st, int den_step,
                   const double *__restrict__ apart, int napart, double *__restrict__ bsum)
 {
-    constexpr int s1 = S - 1, sz1 = SZ - 1;
     constexpr uint32_t PV = (uint32_t)S * S * SZ;  // patch entries per brick / block
     __shared__ double sh[kRedThreads / 64 + 1];
     __shared__ int s_last;  // DS, cg_beta_sum: this workgroup arrived last
@@ -867,30 +761,11 @@ k_cg_update_faces(double *__restrict__ x, double *__restrict__ r, const double *
             double qi;
             if constexpr (PB) {
                 qi = patch_sum8<S, SZ>(brsrc(pb, 8u * (uint32_t)g.nbx * g.nby * g.nbz * PV), g, gx, gy, gz);
-            } else if (gx % s1 == 0 || gy % s1 == 0 || gz % sz1 == 0) {
-                int bxs[2], pxs[2], nxc = 0, bys[2], pys[2], nyc = 0, bzs[2], pzs[2], nzc = 0;
-                const int qx = gx / s1, qy = gy / s1, qz = gz / sz1;
-                if (gx - qx * s1 == 0) {
-                    if (qx - 1 >= 0) { bxs[nxc] = qx - 1; pxs[nxc] = s1; ++nxc; }
-                    if (qx < g.nbx) { bxs[nxc] = qx; pxs[nxc] = 0; ++nxc; }
-                } else { bxs[0] = qx; pxs[0] = gx - qx * s1; nxc = 1; }
-                if (gy - qy * s1 == 0) {
-                    if (qy - 1 >= 0) { bys[nyc] = qy - 1; pys[nyc] = s1; ++nyc; }
-                    if (qy < g.nby) { bys[nyc] = qy; pys[nyc] = 0; ++nyc; }
-                } else { bys[0] = qy; pys[0] = gy - qy * s1; nyc = 1; }
-                if (gz - qz * sz1 == 0) {
-                    if (qz - 1 >= 0) { bzs[nzc] = qz - 1; pzs[nzc] = sz1; ++nzc; }
-                    if (qz < g.nbz) { bzs[nzc] = qz; pzs[nzc] = 0; ++nzc; }
-                } else { bzs[0] = qz; pzs[0] = gz - qz * sz1; nzc = 1; }
+            } else {  // the branchy form: one entry inside a brick's patch, 2 / 4 / 8 on brick faces
                 qi = 0.0;
-                for (int kz = 0; kz < nzc; ++kz)
-                    for (int ky = 0; ky < nyc; ++ky)
-                        for (int kx = 0; kx < nxc; ++kx) {
-                            qi += pb[patch_idx<S, SZ>(g, bxs[kx], bys[ky], bzs[kz], pxs[kx], pys[ky], pzs[kz])];
-                        }
-            } else {  // inside one brick's patch
-                const int qx = gx / s1, qy = gy / s1, qz = gz / sz1;
-                qi = pb[patch_idx<S, SZ>(g, qx, qy, qz, gx - qx * s1, gy - qy * s1, gz - qz * sz1)];
+                brick_holders<S, SZ>(g.nbx, g.nby, g.nbz, gx, gy, gz, [&](int bx, int by, int bz, int px, int py, int pz) {
+                    qi += pb[patch_idx<S, SZ>(g, bx, by, bz, px, py, pz)];
+                });
             }
             // interface planes: add the neighbour rank's partial sums
             if (remote_lo && gz == 0) qi += remote_lo[rem];
@@ -997,6 +872,7 @@ k_hobrick_cg(const double *__restrict__ r, const double *__restrict__ dinv, cons
     const int bz = b / nxy, by = (b - bz * nxy) / g.nbx, bx = b - bz * nxy - by * g.nbx;
     const int gx0 = (S - 1) * bx, gy0 = (S - 1) * by, gz0 = (SZ - 1) * bz;
     const bool lastx = bx == g.nbx - 1, lasty = by == g.nby - 1, lastz = bz == g.nbz - 1;
+    const BrickPos pos{b, bx, by, bz, gx0, gy0, gz0, lastx, lasty, lastz};
     const int Lx = g.Lx, Lxy = g.Lx * g.Ly;
     const uint32_t nl = (uint32_t)Lxy * (uint32_t)g.Lz;
     const auto br = brsrc(r, 8u * nl), bm = brsrc(dinv, 8u * nl), bo = brsrc(d_old, 8u * nl);
@@ -1042,7 +918,7 @@ k_hobrick_cg(const double *__restrict__ r, const double *__restrict__ dinv, cons
             ov[k] = bload(bo, offv[k]);
             ev[k] = 0;
             if (bhas) ev[k] = __builtin_amdgcn_raw_buffer_load_b8(be, in ? gid : kOOB, 0, 0);
-            const bool writer = in && (px < S - 1 || lastx) && (py < S - 1 || lasty) && (pz < SZ - 1 || lastz);
+            const bool writer = is_writer<S, SZ>(px, py, pz, in, pos);
             if constexpr (XF) xv[k] = bload(bxf, writer ? offv[k] : kOOB);
         }
         PatchWalk<S, NT> pw1(tid);
@@ -1055,7 +931,7 @@ k_hobrick_cg(const double *__restrict__ r, const double *__restrict__ dinv, cons
             const bool in = offv[k] != kOOB;
             const double dn = mv[k] * rv[k] + beta * ov[k];  // 0 outside the lattice
             const bool e = ev[k] != 0;
-            const bool writer = in && (px < S - 1 || lastx) && (py < S - 1 || lasty) && (pz < SZ - 1 || lastz);
+            const bool writer = is_writer<S, SZ>(px, py, pz, in, pos);
             const uint32_t woff = writer ? offv[k] : kOOB;
             bstore(bd, woff, dn);
             if constexpr (XF) bstore(bxf, woff, xv[k] + alpha_prev * ov[k]);
@@ -1457,7 +1333,6 @@ k_pack_qplanes(const double *__restrict__ q, const double *__restrict__ face, co
                int lo, int hi, double *__restrict__ out_lo, double *__restrict__ out_hi,
                const KrylovState *__restrict__ st)
 {
-    constexpr int s1 = S - 1;
     if (st->done) return;
     const int n = g.Lx * g.Ly;
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1466,32 +1341,10 @@ k_pack_qplanes(const double *__restrict__ q, const double *__restrict__ face, co
     for (int side = 0; side < 2; ++side) {
         if (side == 0 ? !lo : !hi) continue;
         const int gz = side == 0 ? 0 : g.Lz - 1;
-        double v;
-        if (gx % s1 == 0 || gy % s1 == 0 || gz % s1 == 0) {
-            int bxs[2], pxs[2], nxc = 0, bys[2], pys[2], nyc = 0, bzs[2], pzs[2], nzc = 0;
-            const int qx = gx / s1, qy = gy / s1, qz = gz / s1;
-            if (gx - qx * s1 == 0) {
-                if (qx - 1 >= 0) { bxs[nxc] = qx - 1; pxs[nxc] = s1; ++nxc; }
-                if (qx < g.nbx) { bxs[nxc] = qx; pxs[nxc] = 0; ++nxc; }
-            } else { bxs[0] = qx; pxs[0] = gx - qx * s1; nxc = 1; }
-            if (gy - qy * s1 == 0) {
-                if (qy - 1 >= 0) { bys[nyc] = qy - 1; pys[nyc] = s1; ++nyc; }
-                if (qy < g.nby) { bys[nyc] = qy; pys[nyc] = 0; ++nyc; }
-            } else { bys[0] = qy; pys[0] = gy - qy * s1; nyc = 1; }
-            if (gz - qz * s1 == 0) {
-                if (qz - 1 >= 0) { bzs[nzc] = qz - 1; pzs[nzc] = s1; ++nzc; }
-                if (qz < g.nbz) { bzs[nzc] = qz; pzs[nzc] = 0; ++nzc; }
-            } else { bzs[0] = qz; pzs[0] = gz - qz * s1; nzc = 1; }
-            v = 0.0;
-            for (int kz = 0; kz < nzc; ++kz)
-                for (int ky = 0; ky < nyc; ++ky)
-                    for (int kx = 0; kx < nxc; ++kx) {
-                        v += face[patch_idx<S>(g, bxs[kx], bys[ky], bzs[kz], pxs[kx], pys[ky], pzs[kz])];
-                    }
-        } else {  // inside one brick's patch
-            const int qx = gx / s1, qy = gy / s1, qz = gz / s1;
-            v = face[patch_idx<S>(g, qx, qy, qz, gx - qx * s1, gy - qy * s1, gz - qz * s1)];
-        }
+        double v = 0.0;
+        brick_holders<S>(g.nbx, g.nby, g.nbz, gx, gy, gz, [&](int bx, int by, int bz, int px, int py, int pz) {
+            v += face[patch_idx<S>(g, bx, by, bz, px, py, pz)];
+        });
         (side == 0 ? out_lo : out_hi)[k] = v;
     }
 }
@@ -1504,18 +1357,11 @@ hipError_t launch_pack_qplanes(cdfem_ctx *c, const double *q, hipStream_t s)
     if (!s) s = c->stream;
     // (p = 3, 4: the 2^3-element blocks' cubic patches, S = 2p + 1; p = 4 shares S = 9 with p = 2)
     if (c->p >= 3 && c->hb_ez != kHoBrickEdge) return hipErrorInvalidValue;
-    if (c->p == 1)
-        hipLaunchKernelGGL(k_pack_qplanes<kBrick * 1 + 1>, grid, block, 0, s, q, c->d_face, g,
-                           c->zlo_shared, c->zhi_shared, c->d_if[0], c->d_if[2], c->d_state);
-    else if (c->p == 2 || c->p == 4)
-        hipLaunchKernelGGL(k_pack_qplanes<kBrick * 2 + 1>, grid, block, 0, s, q, c->d_face, g,
-                           c->zlo_shared, c->zhi_shared, c->d_if[0], c->d_if[2], c->d_state);
-    else if (c->p == 3)
-        hipLaunchKernelGGL(k_pack_qplanes<kHoBrickEdge * 3 + 1>, grid, block, 0, s, q, c->d_face, g,
-                           c->zlo_shared, c->zhi_shared, c->d_if[0], c->d_if[2], c->d_state);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
+    return dispatch_value<5, 9, 7>(brick_patch_side(c), hipErrorInvalidValue, [&](auto S) {
+        hipLaunchKernelGGL(k_pack_qplanes<S()>, grid, block, 0, s, q, c->d_face, g, c->zlo_shared, c->zhi_shared,
+                           c->d_if[0], c->d_if[2], c->d_state);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace cdfem

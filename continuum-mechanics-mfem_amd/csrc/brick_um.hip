@@ -155,17 +155,12 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
     }
     const double alpha_prev = XF ? st->alpha : 0.0;
     const int t = threadIdx.x;
-    // launch-local brick -> global brick (a launch covers every g.bzs-th layer from g.bz0)
-    const int bl = brick_id(g), nxy = g.nbx * g.nby;
-    const int bz = g.bz0 + (bl / nxy) * g.bzs;
-    const int b = bl % nxy + nxy * bz;
-    const int bx = b % g.nbx, by = (b / g.nbx) % g.nby;
-    const int gx0 = (S - 1) * bx, gy0 = (S - 1) * by, gz0 = (S - 1) * bz;
-    const bool lastx = bx == g.nbx - 1, lasty = by == g.nby - 1, lastz = bz == g.nbz - 1;
+    const BrickPos pos = brick_pos<S>(g, brick_id(g));
+    const int b = pos.b, gx0 = pos.gx0, gy0 = pos.gy0, gz0 = pos.gz0;
     double den = 0.0;
     // patch gather: every load is issued before any is consumed; out-of-lattice positions of partial
     // bricks use kOOB (loads 0, stores dropped); per position the writer's byte offset and one bit of
-    // dbits for "writer, and its d^2 counts in den" (k_brick_cg of brick_kernels.hip)
+    // dbits for "writer, and its d^2 counts in den" (as the Kronecker form's gather, brick_kernels.hip)
     constexpr int NI = (S3 + 63) / 64;
     const int Lx = g.Lx, Lxy = g.Lx * g.Ly;
     const uint32_t nl = (uint32_t)Lxy * (uint32_t)g.Lz;
@@ -179,9 +174,9 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
         auto axis_word = [](int b0, int e) {
             return 0x4444u | (b0 == 0 ? 2u : 0u) | (e < S ? 3u << (2 * e) : 0u);
         };
-        wx = axis_word(bx, g.Lx - 1 - gx0);
-        wy = axis_word(by, g.Ly - 1 - gy0);
-        wz = axis_word(bz, g.Lz - 1 - gz0);
+        wx = axis_word(pos.bx, g.Lx - 1 - gx0);
+        wy = axis_word(pos.by, g.Ly - 1 - gy0);
+        wz = axis_word(pos.bz, g.Lz - 1 - gz0);
         mv[0] = bload(bm, 8u * (uint32_t)t);
     }
     uint32_t woffv[NI];
@@ -213,7 +208,7 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
         }
         ov[k] = bload(bo, off);
         ev[k] = __builtin_amdgcn_raw_buffer_load_b8(be, in ? gid : kOOB, 0, 0);
-        const bool writer = in && (px < S - 1 || lastx) && (py < S - 1 || lasty) && (pz < S - 1 || lastz);
+        const bool writer = is_writer<S>(px, py, pz, in, pos);
         woffv[k] = writer ? off : kOOB;
         dbits |= (uint32_t)(writer && !(zlo_shared && gz == 0)) << k;
         if constexpr (XF) xv[k] = bload(bxf, woffv[k]);
@@ -240,36 +235,13 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
         if constexpr (k < NST) s_dev[64 * k + t] = dn;
         else dev[k] = dn;
     };
-    auto beta_fold = [&]() -> bool {  // the betanom step of the previous update; true: the solve stops here
-        if (kk > 0) {
-            double B = pv[0];
-            if constexpr (BF == 1) {
-                double v = 0.0;
-#pragma unroll
-                for (int q = 0; q < NPL; ++q) v += pv[q];
-                B = wave_sum(v);
-            }
-            // cg_update_logic's decision (cg_stop_kind), taken identically by every workgroup at the
-            // host's update count kk; workgroup 0 records it at the same kk
-            const bool stop = cg_stop_kind(st, B, kk) != kCgGoOn;
-            if (b == 0 && t == 0) {  // (global brick 0: one launch records, also when a slab is split in two)
-#ifdef CDFEM_DEBUG
-                assert(st->iter == kk);
-#endif
-                cg_update_logic_at(st, B, kk);
-            }
-            if (stop) return true;
-            beta = B / st->nom;
-        }
-        return false;
-    };
     constexpr bool EARLY = um_early(BF, UD);
     if constexpr (BF != 0 && EARLY) {
-        if (beta_fold()) return;
+        if (beta_fold<BF>(pv, st, kk, b, t, beta)) return;
     }
     static_for<0, NI>(gather);
     if constexpr (BF != 0 && !EARLY) {
-        if (beta_fold()) return;
+        if (beta_fold<BF>(pv, st, kk, b, t, beta)) return;
     }
     if constexpr (UD) {
         s_tab[t] = mv[0];
@@ -346,52 +318,20 @@ k_brick_cg(const double *__restrict__ r, const double *__restrict__ dinv, const 
     __syncthreads();
 
     // the brick's whole patch output (interior rows complete, face rows partial; the essential rows carry
-    // the writer's d) -> the patch buffer (patch_idx in 32-bit arithmetic: index = base + pz A + py R + px)
-    {
-        const uint32_t R = (uint32_t)g.nbx * S, A = (uint32_t)g.nby * S * R;
-        const uint32_t base = (uint32_t)bz * S * A + (uint32_t)by * S * R + (uint32_t)bx * S;
-        const auto bp = brsrc(face, 8u * (uint32_t)g.nbx * g.nby * g.nbz * S3);
-        const unsigned to = (unsigned)opaque(t);
-        PatchWalk<S> pw(to);
-#pragma unroll
-        for (int k = 0; k < NI; ++k) {
-            const unsigned i = to + 64 * k;
-            if (k == NI - 1 && i >= S3) break;
-            // an essential row's entry is (A_c d)_i = d_i from its writer (where it counts in den), 0 from the
-            // other bricks; den = sum over positions of d~ y (d~ = 0 on essential rows: every element sharing
-            // a position read the same d~, and masked elements have y = 0) + the writers' d^2 on essential rows:
-            // with the entry formed first, both are d times the entry
-            double v = s_pat[i];
-            const double dk = k < NST ? s_dev[64 * k + to] : dev[k];
-            const double dw = ((dbits >> k) & 1u) ? dk : 0.0;
-            v = ((ebits >> k) & 1u) ? dw : v;
-            den += dk * v;
-            bstore(bp, 8u * (base + (uint32_t)pw.z * A + (uint32_t)pw.y * R + (uint32_t)pw.x), v);
-            pw.next();
-        }
-    }
-    den = wave_sum(den);
-    if (grp <= 1) {
-        if (t == 0) part[b] = den;
-        return;
-    }
-    // grouped partials (den_grp > 1), as k_brick_cg of brick_kernels.hip: write-through partial, agent-scope
-    // arrival count, the group's last brick sums its partials by the fixed wave tree and resets the counter
-    const int gi = b / grp, g0 = gi * grp, gn = min(grp, nbrick - g0);
-    uint32_t prev = 0;
-    if (t == 0) {
-        __hip_atomic_store(&part[b], den, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        prev = __hip_atomic_fetch_add(&gcnt[gi], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    prev = (uint32_t)__shfl((int)prev, 0, 64);
-    if (prev != (uint32_t)(gn - 1)) return;
-    double v = t < gn ? __hip_atomic_load(&part[g0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-    v = wave_sum(v);
-    if (t == 0) {
-        gsum[gi] = v;
-        __hip_atomic_store(&gcnt[gi], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    // the writer's d) -> the patch buffer (patch_store)
+    patch_store<S>(face, g, pos.bx, pos.by, pos.bz, t, [&](int k, unsigned i, int, int, int) {
+        // an essential row's entry is (A_c d)_i = d_i from its writer (where it counts in den), 0 from the
+        // other bricks; den = sum over positions of d~ y (d~ = 0 on essential rows: every element sharing
+        // a position read the same d~, and masked elements have y = 0) + the writers' d^2 on essential rows:
+        // with the entry formed first, both are d times the entry
+        double v = s_pat[i];
+        const double dk = k < NST ? s_dev[i] : dev[k];  // (i = 64 k + lane)
+        const double dw = ((dbits >> k) & 1u) ? dk : 0.0;
+        v = ((ebits >> k) & 1u) ? dw : v;
+        den += dk * v;
+        return v;
+    });
+    den_publish(den, t, b, part, gsum, gcnt, grp, nbrick);
 }
 
 hipError_t launch_brick_um(cdfem_ctx *c, const BrickGeom &g, unsigned nbrick_launch, hipStream_t s, bool whole,

@@ -95,11 +95,7 @@ k_hobrick_um(const double *__restrict__ r, const double *__restrict__ dinv, cons
         bool bhas;
     };
     auto blk_of = [&](int vb) {
-        int b = vb;
-        if (g.xcd) {
-            const unsigned G = (unsigned)nblk, xx = (unsigned)vb % 8, kk = (unsigned)vb / 8, q = G / 8, rr = G % 8;
-            b = (int)(xx * q + (xx < rr ? xx : rr) + kk);
-        }
+        const int b = g.xcd ? xcd_order((unsigned)vb, (unsigned)nblk) : vb;
         const int bz = b / nxy, by = (b - bz * nxy) / g.nbx, bx = b - bz * nxy - by * g.nbx;
         return Blk{b, bx, by, bz, g.bess == nullptr || g.bess[b] != 0};
     };
