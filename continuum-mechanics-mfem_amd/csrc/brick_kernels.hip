@@ -1117,9 +1117,9 @@ static hipError_t brick_cg2_launch(cdfem_ctx *c, const double *r, const double *
             if constexpr ((!kKron && (XF() || BF() || FU() || MX())) || (MX() && !kMX)) return hipErrorInvalidValue;
             else {
                 const auto kern = k_brick_cg<D1, Q1, K, AF(), kKron ? 2 : 1, XF(), BF(), FU(), MX() ? 1 : 0>;
-                CDFEM_LAUNCH_ON(c, whole, run.s, kern, grid, block, 0, r, dinv, d_old, d_new, q, c->d_face, qd,
-                                c->d_ess, T, g, c->zlo_shared, dpart, c->d_state, x, upart, run.nupart, run.kk,
-                                c->d_gsum, c->d_gcnt, grp, nbrick);
+                CDFEM_LAUNCH_ON(c, whole, run.s, kern, grid, block, 0, r, dinv, d_old, d_new, q, c->d_face.get(), qd,
+                                c->d_ess.get(), T, g, c->zlo_shared, dpart, c->d_state.get(), x, upart, run.nupart, run.kk,
+                                c->d_gsum.get(), c->d_gcnt.get(), grp, nbrick);
                 return hipGetLastError();
             }
         });
@@ -1151,8 +1151,8 @@ static hipError_t hobrick_launch(cdfem_ctx *c, const double *r, const double *di
         if constexpr (MF() && !kMF) return hipErrorInvalidValue;
         else {
             const auto kern = k_hobrick_cg<D1, Q1, K, XF(), MF(), EZ>;
-            CDFEM_LAUNCH(c, kern, grid, block, 0, r, dinv, d_old, d_new, c->d_face, c->d_qaff, c->d_ess, T, g, c->sx,
-                         c->sy, c->sz, c->d_hbpart, c->d_state, x, kt, c->zlo_shared);
+            CDFEM_LAUNCH(c, kern, grid, block, 0, r, dinv, d_old, d_new, c->d_face.get(), c->d_qaff.get(), c->d_ess.get(), T, g, c->sx,
+                         c->sy, c->sz, c->d_hbpart.get(), c->d_state.get(), x, kt, c->zlo_shared);
             return hipGetLastError();
         }
     });

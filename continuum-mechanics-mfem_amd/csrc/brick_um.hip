@@ -352,8 +352,8 @@ hipError_t launch_brick_um(cdfem_ctx *c, const BrickGeom &g, unsigned nbrick_lau
     dispatch_value<0, 1, 2>(kk < 0 ? 0 : bs ? 2 : 1, 0, [&](auto BF) {
         dispatch_bools(x != nullptr, full, ud, [&](auto XF, auto FU, auto UD) {
             const auto kern = k_brick_cg<XF(), BF(), FU(), UD()>;
-            CDFEM_LAUNCH_ON(c, whole, s, kern, grid, block, 0, r, dinv, d_old, d_new, c->d_face, c->d_uelem, c->d_ess,
-                            g, c->zlo_shared, dpart, c->d_state, x, upart, nupart, kk, c->d_gsum, c->d_gcnt, c->den_grp,
+            CDFEM_LAUNCH_ON(c, whole, s, kern, grid, block, 0, r, dinv, d_old, d_new, c->d_face.get(), c->d_uelem.get(), c->d_ess.get(),
+                            g, c->zlo_shared, dpart, c->d_state.get(), x, upart, nupart, kk, c->d_gsum.get(), c->d_gcnt.get(), c->den_grp,
                             c->nblk);
         });
         return 0;
@@ -397,11 +397,7 @@ k_uniform_elem(const double *__restrict__ gaff, const Tab<D1, Q1> T, double *__r
 
 hipError_t setup_uniform_elem(cdfem_ctx *c)
 {
-    if (c->d_uelem) {
-        const hipError_t e = hipFree(c->d_uelem);
-        c->d_uelem = nullptr;
-        if (e != hipSuccess) return e;
-    }
+    c->d_uelem.reset();
     if (!c->pa_uniform || !c->structured || c->qlay != 0 || c->dim != 3 || pa_af(c) != 2 || c->p != 2 ||
         c->rule_op.q1 != 4 || c->ncomp < 1 || (c->kinds != 7 && c->kinds != 5))
         return hipSuccess;
@@ -414,10 +410,10 @@ hipError_t setup_uniform_elem(cdfem_ctx *c)
     for (double v : g0) gmax = std::max(gmax, std::fabs(v));
     // one scratch allocation: the flag, then the N x N matrix
     constexpr int N = kUmN;
-    void *scratch = nullptr;
-    if ((e = hipMalloc(&scratch, sizeof(double) * (N * N + 1))) != hipSuccess) return e;
-    int *bad = static_cast<int *>(scratch);
-    double *A = static_cast<double *>(scratch) + 1;
+    DevBuf<double> scratch;
+    scratch.alloc(N * N + 1);
+    int *bad = reinterpret_cast<int *>(scratch.get());
+    double *A = scratch + 1;
     int hbad = 0;
     const int nslots = c->nblk * kLanes;
     e = hipMemsetAsync(bad, 0, sizeof(int), c->stream);
@@ -437,9 +433,7 @@ hipError_t setup_uniform_elem(cdfem_ctx *c)
         if (e == hipSuccess) e = hipMemcpyAsync(h.data(), A, sizeof(double) * N * N, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     }
-    const hipError_t ef = hipFree(scratch);
     if (e != hipSuccess) return e;
-    if (ef != hipSuccess) return ef;
     if (hbad) return hipSuccess;  // not uniform: the Kronecker form
     // the A operands of v_mfma_f64_16x16x4_f64 in lane order, rows in kUmRow's order:
     // [mt][ks][lane] = A[kUmRow[16 mt + (lane & 15)]][4 ks + (lane >> 4)]
@@ -449,14 +443,11 @@ hipError_t setup_uniform_elem(cdfem_ctx *c)
                 const int i = kUmRow[16 * mt + (l & 15)], j = 4 * ks + (l >> 4);
                 op[(mt * 7 + ks) * 64 + l] = (i >= 0 && j < N) ? h[i * N + j] : 0.0;
             }
-    void *d = nullptr;
-    if ((e = hipMalloc(&d, sizeof(double) * op.size())) != hipSuccess) return e;
+    DevBuf<double> d;
+    d.alloc(op.size());
     e = hipMemcpy(d, op.data(), sizeof(double) * op.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return e;
-    }
-    c->d_uelem = static_cast<double *>(d);
+    if (e != hipSuccess) return e;
+    c->d_uelem = std::move(d);
     return hipSuccess;
 }
 
@@ -516,19 +507,15 @@ k_udiag_check(const double *__restrict__ dinv, const uint8_t *__restrict__ ess, 
 hipError_t setup_uniform_diag(cdfem_ctx *c)
 {
     hipError_t e = hipSuccess;
-    if (c->d_udiag) {
-        e = hipFree(c->d_udiag);
-        c->d_udiag = nullptr;
-        if (e != hipSuccess) return e;
-    }
+    c->d_udiag.reset();
     c->udiag_bitwise = false;
     if (c->d_uelem == nullptr || !c->structured || c->dim != 3 || c->p != 2 || c->perm_space ||
         c->nl != c->Lx * c->Ly * c->Lz || c->nl >= ((int64_t)1 << 31))
         return hipSuccess;
     // one allocation: the table, the classes' first indices, the two flags
-    void *buf = nullptr;
-    if ((e = hipMalloc(&buf, sizeof(double) * kUdiagN + sizeof(uint32_t) * (kUdiagN + 2))) != hipSuccess) return e;
-    double *tab = static_cast<double *>(buf);
+    DevBuf<double> buf;
+    buf.alloc(kUdiagN + (kUdiagN + 2 + 1) / 2);  // (the 32-bit words rounded up to whole doubles)
+    double *tab = buf;
     uint32_t *first = reinterpret_cast<uint32_t *>(tab + kUdiagN);
     int *flags = reinterpret_cast<int *>(first + kUdiagN);
     int hflags[2] = {1, 1};
@@ -544,11 +531,8 @@ hipError_t setup_uniform_diag(cdfem_ctx *c)
     }
     if (e == hipSuccess) e = hipMemcpyAsync(hflags, flags, sizeof(hflags), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || hflags[0]) {  // not class-constant: the solve streams the vector
-        const hipError_t ef = hipFree(buf);
-        return e != hipSuccess ? e : ef;
-    }
-    c->d_udiag = tab;
+    if (e != hipSuccess || hflags[0]) return e;  // not class-constant: the solve streams the vector
+    c->d_udiag = std::move(buf);
     c->udiag_bitwise = hflags[1] == 0;
     return hipSuccess;
 }

@@ -20,17 +20,36 @@
 
 using namespace cdfem;
 
+// ---- the raw resources behind the handles (handles.hpp) -----------------------------------------
+void *cdfem::raw_device_alloc(size_t bytes)
+{
+    void *p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    return p;
+}
+void cdfem::raw_device_free(void *p) noexcept { (void)hipFree(p); }
+void *cdfem::raw_pinned_alloc(size_t bytes)
+{
+    void *p = nullptr;
+    HIPCHK(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+    return p;
+}
+void cdfem::raw_pinned_free(void *p) noexcept { (void)hipHostFree(p); }
+hipEvent_t cdfem::raw_event_create(bool timing)
+{
+    hipEvent_t e = nullptr;
+    HIPCHK(hipEventCreateWithFlags(&e, timing ? hipEventDefault : hipEventDisableTiming));
+    return e;
+}
+void cdfem::raw_event_destroy(hipEvent_t e) noexcept { (void)hipEventDestroy(e); }
+
 // ---- profiling helpers ---------------------------------------------------------------------------
 void cdfem::prof_mark(cdfem_ctx *c, int k, bool begin)
 {
     if (!c->profile || !((c->prof_mask >> k) & 1u)) return;
     ProfileSlot &s = c->prof[k];
     const size_t need = (size_t)(s.used + 1) * 2;
-    while (s.ev.size() < need) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        s.ev.push_back(e);
-    }
+    while (s.ev.size() < need) s.ev.emplace_back().create(true);
     if (begin) {
         // recorded now AND armed: a CDFEM_LAUNCH before the end mark re-records the pair tightly
         // around its own dispatch; any other launch leaves the plain event interval
@@ -99,60 +118,12 @@ static bool mesh_is_affine(int dim, int64_t ne, const double *V)
     return true;
 }
 
+// a new mesh starts from nothing: every buffer of the old one freed, every flag at its initialiser
 void free_mesh(cdfem_ctx *c)
 {
-    dfree(c->d_verts); dfree(c->d_map); dfree(c->d_e2l_off); dfree(c->d_e2l_pos);
-    dfree(c->d_ess); dfree(c->d_ess_list); dfree(c->d_qd); dfree(c->d_qaff); dfree(c->d_geom); dfree(c->d_hgeom); dfree(c->d_Ye); dfree(c->d_dinv);
-    for (auto &w : c->d_w) dfree(w);
-    dfree(c->d_part); dfree(c->d_tpart); dfree(c->d_gm); dfree(c->d_gm_part); dfree(c->d_ktab);
-    dfree(c->d_bcgs); dfree(c->d_bcgs_part);
-    c->bcgs_n = -1;
-    c->ktab_key = -1;  // rebuilt (and reallocated) by the next k_apply3d_ktile launch
-    dfree(c->d_perm); dfree(c->d_face); dfree(c->d_ones); dfree(c->d_dalt);
-    for (auto &b : c->d_if) dfree(b);
-    dfree(c->d_stab); dfree(c->d_stab_lf); dfree(c->d_rowptr); dfree(c->d_cols); dfree(c->d_diagpos); dfree(c->d_coff);
-    dfree(c->d_cpos); dfree(c->d_vals); dfree(c->d_vals_c); dfree(c->d_Ee);
-    dfree(c->d_sptr); dfree(c->d_srows); dfree(c->d_scols); dfree(c->d_smap); dfree(c->d_sdel); dfree(c->d_svals);
-    dfree(c->d_swide);
-    dfree(c->d_uelem);
-    dfree(c->d_udiag);
-    dfree(c->d_hoelem);
-    c->sell_nnz_wide = 0;
-    dfree(c->d_hptr); dfree(c->d_hidx); dfree(c->d_sloc);
-    c->lds_rows = 0;
-    c->lds_max = 0;
-    c->sell_lpr = 1;
-    dfree(c->d_rperm); dfree(c->d_pv[0]); dfree(c->d_pv[1]); dfree(c->d_dinv_p);
-    dfree(c->d_svals_c);
-    dfree(c->d_lfq);
-    c->lfq_cap = 0;
     ilu_free(c);
     partition_free(c);
-    c->nslices = c->nstored = 0;
-    c->sell_windowed = false;
-    c->geom = 0;
-    c->fa_ready = false;
-    c->nnz = 0;
-    c->h_verts.clear();
-    c->h_sxi_d.clear();
-    c->h_sxi_cm.clear();
-    c->h_sxi_lf.clear();
-    c->zlo_shared = c->zhi_shared = 0;
-    c->gm_cap = 0;
-    c->mesh_ready = c->pa_ready = c->dinv_ready = false;
-    c->structured = false;
-    c->epencil = false;
-    c->slab_nl_max = 0;
-    c->slab_nb_max = 0;
-    dfree(c->d_small);
-    dfree(c->d_gsum);
-    dfree(c->d_gcnt);
-    dfree(c->d_bsum);
-    c->gsum_cap = 0;
-    c->den_grp = 1;
-    dfree(c->d_hbpart);
-    dfree(c->d_bess);
-    c->hb_nblk = 0;
+    static_cast<MeshState &>(*c) = MeshState{};
 }
 
 // per brick (edge E elements in x and y, EZ in z; nb* bricks per axis): 1 if a lattice dof of its patch
@@ -173,8 +144,7 @@ static void upload_brick_ess(cdfem_ctx *c, int E, int EZ, int nbx, int nby, int 
                     }
                 has[((size_t)bz * nby + by) * nbx + bx] = h;
             }
-    dfree(c->d_bess);
-    c->d_bess = dalloc<uint8_t>(has.size());
+    c->d_bess.alloc(has.size());
     HIPCHK(hipMemcpy(c->d_bess, has.data(), has.size(), hipMemcpyHostToDevice));
 }
 
@@ -210,18 +180,12 @@ void build_layout(cdfem_ctx *c, const std::vector<int32_t> &perm)
             pos[fill[g]++] = (int32_t)eidx(e, l);
         }
     }
-    dfree(c->d_map); dfree(c->d_e2l_off); dfree(c->d_e2l_pos); dfree(c->d_perm); dfree(c->d_Ye);
-    dfree(c->d_part);
-    c->d_map = dalloc<int32_t>(map.size());
-    c->d_e2l_off = dalloc<int32_t>(nl + 1);
-    c->d_e2l_pos = dalloc<int32_t>(pos.size());
-    c->d_perm = dalloc<int32_t>(perm.size());
-    c->d_Ye = dalloc<double>((size_t)c->nblk * nd * kLanes);
-    c->d_part = dalloc<double>((size_t)c->red_blocks + c->nblk + 64 * 8192 + 16384);
-    HIPCHK(hipMemcpyAsync(c->d_map, map.data(), map.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_e2l_off, cnt.data(), (nl + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_e2l_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_perm, perm.data(), perm.size() * 4, hipMemcpyHostToDevice, c->stream));
+    upload(c, c->d_map, map);
+    upload(c, c->d_e2l_off, cnt);
+    upload(c, c->d_e2l_pos, pos);
+    upload(c, c->d_perm, perm);
+    c->d_Ye.alloc((size_t)c->nblk * nd * kLanes);
+    c->d_part.alloc((size_t)c->red_blocks + c->nblk + 64 * 8192 + 16384);
     HIPCHK(hipMemsetAsync(c->d_Ye, 0, (size_t)c->nblk * nd * kLanes * sizeof(double), c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
 }
@@ -299,12 +263,16 @@ int cdfem_create(int device, cdfem_ctx **out)
     cdfem_ctx *c = new (std::nothrow) cdfem_ctx();
     if (!c) return CDFEM_ERR_HIP;
     c->device = device;
-    if (hipSetDevice(device) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&c->d_state, sizeof(KrylovState)) != hipSuccess ||
-        hipMemset(c->d_state, 0, sizeof(KrylovState)) != hipSuccess ||
-        hipHostMalloc(&c->h_state, sizeof(KrylovState), hipHostMallocDefault) != hipSuccess ||
-        hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
+    const int rc = guarded(c, [&] {
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+        c->d_state.alloc(1);
+        HIPCHK(hipMemset(c->d_state, 0, sizeof(KrylovState)));
+        c->h_state.alloc(1);
+        HIPCHK(hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, device));
+        return CDFEM_OK;
+    });
+    if (rc != CDFEM_OK) {
         cdfem_destroy(c);
         return CDFEM_ERR_HIP;
     }
@@ -312,29 +280,13 @@ int cdfem_create(int device, cdfem_ctx **out)
     return CDFEM_OK;
 }
 
+// the context's members release what they own: the buffers and events first, the streams last
 void cdfem_destroy(cdfem_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    free_mesh(c);
     comm_destroy(c);
-    if (c->d_state) (void)hipFree(c->d_state);
-    if (c->h_state) (void)hipHostFree(c->h_state);
-    if (c->d_gmst) (void)hipFree(c->d_gmst);
-    if (c->h_gmpoll) (void)hipHostFree(c->h_gmpoll);
-    for (auto e : c->gm_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->d_bcst) (void)hipFree(c->d_bcst);
-    if (c->h_bcpoll) (void)hipHostFree(c->h_bcpoll);
-    for (auto e : c->bc_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &s : c->prof)
-        for (auto e : s.ev) (void)hipEventDestroy(e);
-    for (auto e : c->ov_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -352,7 +304,7 @@ int cdfem_alloc(cdfem_ctx *c, size_t bytes, void **dptr)
 {
     return guarded(c, [&] {
         if (!dptr) throw ArgError("dptr is null");
-        HIPCHK(hipMalloc(dptr, bytes ? bytes : 1));
+        *dptr = raw_device_alloc(bytes ? bytes : 1);  // the caller's to release (cdfem_free)
         return CDFEM_OK;
     });
 }
@@ -430,17 +382,11 @@ int cdfem_mesh_upload(cdfem_ctx *c, int dim, int order, int ne, const double *el
         c->n_ess = (int)ess_list.size();
 
         c->mesh_affine = mesh_is_affine(dim, ne, elem_verts);
-        c->d_verts = dalloc<double>((size_t)ne * c->nv * dim);
-        c->d_ess = dalloc<uint8_t>(nldofs);
-        c->d_ess_list = dalloc<int32_t>(ess_list.size());
-        c->d_dinv = dalloc<double>(nldofs);
-        for (auto &w : c->d_w) w = dalloc<double>(nldofs);
-        HIPCHK(hipMemcpyAsync(c->d_verts, elem_verts, (size_t)ne * c->nv * dim * sizeof(double),
-                              hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->d_ess, c->h_ess.data(), nldofs, hipMemcpyHostToDevice, c->stream));
-        if (!ess_list.empty())
-            HIPCHK(hipMemcpyAsync(c->d_ess_list, ess_list.data(), ess_list.size() * 4,
-                                  hipMemcpyHostToDevice, c->stream));
+        upload(c, c->d_verts, elem_verts, (size_t)ne * c->nv * dim);
+        upload(c, c->d_ess, c->h_ess);
+        upload(c, c->d_ess_list, ess_list);
+        c->d_dinv.alloc(nldofs);
+        for (auto &w : c->d_w) w.alloc(nldofs);
         // element blocks of 64 in input order (identity permutation, padded)
         std::vector<int32_t> perm((size_t)c->nblk * kLanes, -1);
         for (int e = 0; e < ne; ++e) perm[e] = e;
@@ -484,7 +430,7 @@ int cdfem_mesh_set_structured(cdfem_ctx *c, int nx, int ny, int nz)
             c->hb_nbz = (nz + c->hb_ez - 1) / c->hb_ez;
             c->hb_nblk = c->hb_nbx * c->hb_nby * c->hb_nbz;
             upload_brick_ess(c, kHoBrickEdge, c->hb_ez, c->hb_nbx, c->hb_nby, c->hb_nbz);
-            dfree(c->d_face);  // the high-order brick CG's patch buffer: allocated by its first solve
+            c->d_face.reset();  // the high-order brick CG's patch buffer: allocated by its first solve
             return CDFEM_OK;
         }
         c->nbx = (nx + kBrick - 1) / kBrick;
@@ -505,10 +451,9 @@ int cdfem_mesh_set_structured(cdfem_ctx *c, int nx, int ny, int nz)
         build_layout(c, perm);
         const int S = kBrick * p + 1;
         c->nface = 2 * S * S + (S - 2) * (4 * S - 4);
-        dfree(c->d_face);
         // per brick: the Mult's face partials (nface) or the CG apply's whole patch output (S^3)
-        c->d_face = dalloc<double>((size_t)c->nblk * std::max(c->nface, S * S * S));
-        dfree(c->d_qd);
+        c->d_face.alloc((size_t)c->nblk * std::max(c->nface, S * S * S));
+        c->d_qd.reset();
         c->structured = true;
         c->pa_ready = false;
         c->dinv_ready = false;
@@ -534,12 +479,8 @@ int cdfem_set_slab(cdfem_ctx *c, int zlo_shared, int zhi_shared)
             std::vector<double> h((size_t)2 * R, 0.0);
             h[2 * c->rank] = (double)c->nl;
             h[2 * c->rank + 1] = (double)brick_count(c);
-            double *d = dalloc<double>(h.size());
-            struct Free {
-                double *p;
-                ~Free() { (void)hipFree(p); }
-            } fr{d};
-            HIPCHK(hipMemcpyAsync(d, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
+            DevBuf<double> d;
+            upload(c, d, h);
             comm_allreduce(c, d, 2 * R);
             HIPCHK(hipMemcpyAsync(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
@@ -550,8 +491,7 @@ int cdfem_set_slab(cdfem_ctx *c, int zlo_shared, int zhi_shared)
         }
         c->skip_lo = c->zlo_shared ? n : 0;  // the lower plane is owned by the rank below
         for (auto &b : c->d_if) {
-            dfree(b);
-            b = dalloc<double>(n);
+            b.alloc(n);
             HIPCHK(hipMemsetAsync(b, 0, n * 8, c->stream));
         }
         c->dinv_ready = false;
@@ -620,20 +560,13 @@ int cdfem_set_shared(cdfem_ctx *c, int n_nbr, const int32_t *nbr_ranks, const in
         c->nbr_off = off;
         c->h_sh_idx = idx;
         c->n_shd = (int32_t)dofs.size();
-        c->d_sh_idx = dalloc<int32_t>(ntot);
-        c->d_sh_send = dalloc<double>(ntot);
-        c->d_sh_recv = dalloc<double>(ntot);
-        c->d_shd = dalloc<int32_t>(dofs.size());
-        c->d_shd_off = dalloc<int32_t>(soff.size());
-        c->d_shd_src = dalloc<int32_t>(src.size());
-        c->d_shd_owner = dalloc<int32_t>(owner.size());
-        if (ntot) HIPCHK(hipMemcpyAsync(c->d_sh_idx, idx.data(), ntot * 4, hipMemcpyHostToDevice, c->stream));
-        if (!dofs.empty()) {
-            HIPCHK(hipMemcpyAsync(c->d_shd, dofs.data(), dofs.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->d_shd_src, src.data(), src.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->d_shd_owner, owner.data(), owner.size() * 4, hipMemcpyHostToDevice, c->stream));
-        }
-        HIPCHK(hipMemcpyAsync(c->d_shd_off, soff.data(), soff.size() * 4, hipMemcpyHostToDevice, c->stream));
+        upload(c, c->d_sh_idx, idx);
+        c->d_sh_send.alloc(ntot);
+        c->d_sh_recv.alloc(ntot);
+        upload(c, c->d_shd, dofs);
+        upload(c, c->d_shd_off, soff);
+        upload(c, c->d_shd_src, src);
+        upload(c, c->d_shd_owner, owner);
         HIPCHK(hipStreamSynchronize(c->stream));
         c->part_mode = 2;
         c->skip_lo = n_not_owned;
@@ -662,14 +595,13 @@ int cdfem_check_shared(cdfem_ctx *c, const int64_t *l2g)
         for (int k = 0; k < nn; ++k) cs[k] = (double)(c->nbr_off[k + 1] - c->nbr_off[k]);
         // (the counts travel in the send / recv buffers of the shared sums when they hold nn slots,
         //  else in scratch freed on every exit path, exceptions from the exchange included)
-        struct Scratch {
-            double *p = nullptr;
-            ~Scratch() { dfree(p); }
-        } sa, sb;
+        DevBuf<double> sa, sb;
         double *d_a = c->d_sh_send, *d_b = c->d_sh_recv;
         if (ntot < nn) {
-            sa.p = d_a = dalloc<double>(nn);
-            sb.p = d_b = dalloc<double>(nn);
+            sa.alloc(nn);
+            sb.alloc(nn);
+            d_a = sa;
+            d_b = sb;
         }
         HIPCHK(hipMemcpyAsync(d_a, cs.data(), nn * 8, hipMemcpyHostToDevice, c->stream));
         comm_exchange_nbr_buf(c, off1, d_a, d_b, c->stream);
@@ -802,23 +734,23 @@ int cdfem_quadrature_points(cdfem_ctx *c, int rule, double *xyz, int where)
         const Rule1D &r = rule == CDFEM_RULE_LINEARFORM ? c->rule_lf : rule == CDFEM_RULE_ERROR ? c->rule_err
                                                                                                  : c->rule_op;
         const size_t n = (size_t)c->ne * nq_of(c, r) * c->dim;
-        double *d = where == CDFEM_DEVICE ? xyz : dalloc<double>(n);
+        DevBuf<double> tmp;
+        if (where != CDFEM_DEVICE) tmp.alloc(n);
+        double *d = where == CDFEM_DEVICE ? xyz : tmp.get();
         HIPCHK(launch_quad_points(c, r, d));
         if (where != CDFEM_DEVICE) {
             HIPCHK(hipMemcpyAsync(xyz, d, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
-            dfree(d);
         }
         return CDFEM_OK;
     });
 }
 
-// device copy of an optional host coefficient array (freed by the caller)
-static double *upload_opt(cdfem_ctx *c, const double *h, size_t n)
+// device copy of an optional host coefficient array (null without one)
+static DevBuf<double> upload_opt(cdfem_ctx *c, const double *h, size_t n)
 {
-    if (!h) return nullptr;
-    double *d = dalloc<double>(n);
-    HIPCHK(hipMemcpyAsync(d, h, n * 8, hipMemcpyHostToDevice, c->stream));
+    DevBuf<double> d;
+    if (h) upload(c, d, h, n);
     return d;
 }
 
@@ -840,24 +772,23 @@ static int pa_setup_form(cdfem_ctx *c, const cdfem_form_coeffs *f)
             throw UnsupportedError("no PA apply kernel built for dim=" + std::to_string(c->dim) +
                                    " order=" + std::to_string(c->p));
         const unsigned kinds = f->kinds;
-        dfree(c->d_qd);
         c->kinds = kinds;
         c->ncomp = ((kinds & CDFEM_DIFFUSION) ? c->dim * (c->dim + 1) / 2 : 0) +
                    ((kinds & CDFEM_CONVECTION) ? c->dim : 0) + ((kinds & CDFEM_MASS) ? 1 : 0);
         const int nq = nq_of(c, c->rule_op);
-        c->d_qd = c->qlay == 1 ? dalloc<double>((size_t)c->ne * c->rule_op.q1 * qd_ho_plane(c->ncomp, c->rule_op.q1))
-                               : dalloc<double>((size_t)c->nblk * nq * c->ncomp * kLanes);
+        c->d_qd.alloc(c->qlay == 1 ? (size_t)c->ne * c->rule_op.q1 * qd_ho_plane(c->ncomp, c->rule_op.q1)
+                                   : (size_t)c->nblk * nq * c->ncomp * kLanes);
         const size_t neq = (size_t)c->ne * nq;
-        dfree(c->d_qaff);
+        c->d_qaff.reset();
         if (c->pa_affine && c->mesh_affine && !f->kappa_q && !f->kappa_mat_q && !f->conv_q && !f->mass_q)
-            c->d_qaff = dalloc<double>((size_t)c->nblk * c->ncomp * kLanes);
+            c->d_qaff.alloc((size_t)c->nblk * c->ncomp * kLanes);
         // pa_geom: a hex mesh the affine forms did not take, constant coefficients, the thread-per-element
         // applies on the operator rule: the element geometry next to the stream (which the diagonal, the
         // linear system and a later pa_geom 0 still read).  Any other case keeps the stream alone.
-        dfree(c->d_geom);
+        c->d_geom.reset();
         if (c->pa_geom && c->d_qaff == nullptr && c->dim == 3 && c->qlay == 0 && (c->p == 1 || c->p == 2) &&
             c->rule_op.q1 == c->p + 2 && !f->kappa_q && !f->kappa_mat_q && !f->conv_q && !f->mass_q) {
-            c->d_geom = dalloc<double>(GeomLayout::kHdr + (size_t)c->nblk * GeomLayout::kNC * kLanes);
+            c->d_geom.alloc(GeomLayout::kHdr + (size_t)c->nblk * GeomLayout::kNC * kLanes);
             double hdr[GeomLayout::kHdr] = {};
             hdr[GeomLayout::hKappa] = f->kappa;
             for (int i = 0; i < 3; ++i) hdr[GeomLayout::hConv + i] = ((kinds & CDFEM_CONVECTION) && f->conv) ? f->alpha * f->conv[i] : 0.0;
@@ -868,10 +799,10 @@ static int pa_setup_form(cdfem_ctx *c, const cdfem_form_coeffs *f)
         }
         // ho_geom: the same for the p = 3, 4 tile apply, element-major (whether the apply takes it also
         // depends on ho_mfma when it runs: ho_geom_on)
-        dfree(c->d_hgeom);
+        c->d_hgeom.reset();
         if (c->ho_geom && c->d_qaff == nullptr && c->dim == 3 && c->qlay == 1 && (c->p == 3 || c->p == 4) &&
             c->rule_op.q1 == c->p + 2 && !f->kappa_q && !f->kappa_mat_q && !f->conv_q && !f->mass_q) {
-            c->d_hgeom = dalloc<double>(GeomLayout::kHdr + (size_t)c->ne * HoGeomLayout::kNC);
+            c->d_hgeom.alloc(GeomLayout::kHdr + (size_t)c->ne * HoGeomLayout::kNC);
             double hdr[GeomLayout::kHdr] = {};
             hdr[GeomLayout::hKappa] = f->kappa;
             for (int i = 0; i < 3; ++i) hdr[GeomLayout::hConv + i] = ((kinds & CDFEM_CONVECTION) && f->conv) ? f->alpha * f->conv[i] : 0.0;
@@ -880,11 +811,10 @@ static int pa_setup_form(cdfem_ctx *c, const cdfem_form_coeffs *f)
             HIPCHK(hipMemcpy(c->d_hgeom, hdr, sizeof(hdr), hipMemcpyHostToDevice));
             HIPCHK(launch_setup_hgeom(c));
         }
-        double *dk = upload_opt(c, f->kappa_q, neq), *dkm = upload_opt(c, f->kappa_mat_q, neq * c->dim * (c->dim + 1) / 2);
-        double *dc = upload_opt(c, f->conv_q, neq * c->dim), *dm = upload_opt(c, f->mass_q, neq);
+        const DevBuf<double> dk = upload_opt(c, f->kappa_q, neq), dkm = upload_opt(c, f->kappa_mat_q, neq * c->dim * (c->dim + 1) / 2);
+        const DevBuf<double> dc = upload_opt(c, f->conv_q, neq * c->dim), dm = upload_opt(c, f->mass_q, neq);
         HIPCHK(launch_setup_qdata(c, dk, dkm, f->kappa, f->alpha, f->conv, dc, dm, f->mass));
         HIPCHK(hipStreamSynchronize(c->stream));
-        dfree(dk); dfree(dkm); dfree(dc); dfree(dm);
         HIPCHK(setup_uniform_elem(c));  // pa_uniform: the common element matrix of a uniform box
         c->pa_ready = true;
         c->fa_ready = false;
@@ -986,26 +916,17 @@ int cdfem_mesh_upload_simplex(cdfem_ctx *c, int dim, int order, int ne, const do
             std::vector<int32_t> fill(cnt.begin(), cnt.end() - 1);
             for (int64_t k = 0; k < (int64_t)ne * nd; ++k) pos[fill[c->h_dofs[k]]++] = (int32_t)k;
         }
-        c->d_e2l_off = dalloc<int32_t>(nldofs + 1);
-        c->d_e2l_pos = dalloc<int32_t>(pos.size());
-        c->d_Ye = dalloc<double>(pos.size());
-        HIPCHK(hipMemcpyAsync(c->d_e2l_off, cnt.data(), (nldofs + 1) * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->d_e2l_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, c->stream));
-        c->d_stab_lf = dalloc<double>(tab_lf.size());
-        HIPCHK(hipMemcpyAsync(c->d_stab_lf, tab_lf.data(), tab_lf.size() * 8, hipMemcpyHostToDevice, c->stream));
-        c->d_stab = dalloc<double>(tab.size());
-        c->d_verts = dalloc<double>(c->h_verts.size());
-        c->d_ess = dalloc<uint8_t>(nldofs);
-        c->d_ess_list = dalloc<int32_t>(ess_list.size());
-        c->d_dinv = dalloc<double>(nldofs);
-        for (auto &v : c->d_w) v = dalloc<double>(nldofs);
-        c->d_part = dalloc<double>((size_t)c->red_blocks + kSpmvMaxBlocks + 16384);
-        HIPCHK(hipMemcpyAsync(c->d_stab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->d_verts, c->h_verts.data(), c->h_verts.size() * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->d_ess, c->h_ess.data(), nldofs, hipMemcpyHostToDevice, c->stream));
-        if (!ess_list.empty())
-            HIPCHK(hipMemcpyAsync(c->d_ess_list, ess_list.data(), ess_list.size() * 4, hipMemcpyHostToDevice,
-                                  c->stream));
+        upload(c, c->d_e2l_off, cnt);
+        upload(c, c->d_e2l_pos, pos);
+        c->d_Ye.alloc(pos.size());
+        upload(c, c->d_stab_lf, tab_lf);
+        upload(c, c->d_stab, tab);
+        upload(c, c->d_verts, c->h_verts);
+        upload(c, c->d_ess, c->h_ess);
+        upload(c, c->d_ess_list, ess_list);
+        c->d_dinv.alloc(nldofs);
+        for (auto &v : c->d_w) v.alloc(nldofs);
+        c->d_part.alloc((size_t)c->red_blocks + kSpmvMaxBlocks + 16384);
         HIPCHK(hipStreamSynchronize(c->stream));
         c->mesh_ready = true;
         return CDFEM_OK;
@@ -1045,73 +966,58 @@ static int fa_setup_form(cdfem_ctx *c, const cdfem_form_coeffs *f)
                                          c->dim, xyz.empty() ? nullptr : xyz.data(), c->sell_window, 0, 1);
                 }
             }
-            c->nnz = P.nnz;
-            c->d_rowptr = dalloc<int32_t>(P.rowptr.size());
-            c->d_cols = dalloc<int32_t>(P.cols.size());
-            c->d_diagpos = dalloc<int32_t>(P.diagpos.size());
-            c->d_coff = dalloc<int32_t>(P.coff.size());
-            c->d_cpos = dalloc<int32_t>(P.cpos.size());
-            c->d_vals = dalloc<double>(c->nnz);
-            c->d_vals_c = dalloc<double>(c->nnz);
-            c->d_Ee = dalloc<double>((size_t)c->nblk * c->nd * c->nd * kLanes);
-            HIPCHK(hipMemcpyAsync(c->d_rowptr, P.rowptr.data(), P.rowptr.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->d_cols, P.cols.data(), P.cols.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->d_diagpos, P.diagpos.data(), P.diagpos.size() * 4, hipMemcpyHostToDevice,
-                                  c->stream));
-            HIPCHK(hipMemcpyAsync(c->d_coff, P.coff.data(), P.coff.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->d_cpos, P.cpos.data(), P.cpos.size() * 4, hipMemcpyHostToDevice, c->stream));
-            c->nslices = (int64_t)P.sptr.size() - 1;
-            if ((c->nslices + 3) / 4 + 8 > kSpmvMaxBlocks) throw UnsupportedError("matrix too large for the SpMV grid");
-            c->nstored = P.sptr.back();
-            c->d_sptr = dalloc<int32_t>(P.sptr.size());
-            c->d_srows = dalloc<int32_t>(P.srows.size());
-            c->d_scols = dalloc<int32_t>(P.scols.size());
-            c->d_smap = dalloc<int32_t>(P.smap.size());
-            c->d_svals = dalloc<double>(c->nstored);
-            c->d_svals_c = dalloc<double>(c->nstored);
-            HIPCHK(hipMemcpyAsync(c->d_sptr, P.sptr.data(), P.sptr.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->d_srows, P.srows.data(), P.srows.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->d_scols, P.scols.data(), P.scols.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->d_smap, P.smap.data(), P.smap.size() * 4, hipMemcpyHostToDevice, c->stream));
-            c->sell_windowed = P.windowed;
+            const int64_t nslices = (int64_t)P.sptr.size() - 1;
+            if ((nslices + 3) / 4 + 8 > kSpmvMaxBlocks) throw UnsupportedError("matrix too large for the SpMV grid");
+            // built aside and moved into the context whole, after the last call that can throw
+            FaDeviceState F;
+            F.nnz = P.nnz;
+            upload(c, F.d_rowptr, P.rowptr);
+            upload(c, F.d_cols, P.cols);
+            upload(c, F.d_diagpos, P.diagpos);
+            upload(c, F.d_coff, P.coff);
+            upload(c, F.d_cpos, P.cpos);
+            F.d_vals.alloc(F.nnz);
+            F.d_vals_c.alloc(F.nnz);
+            F.d_Ee.alloc((size_t)c->nblk * c->nd * c->nd * kLanes);
+            F.nslices = nslices;
+            F.nstored = P.sptr.back();
+            upload(c, F.d_sptr, P.sptr);
+            upload(c, F.d_srows, P.srows);
+            upload(c, F.d_scols, P.scols);
+            upload(c, F.d_smap, P.smap);
+            F.d_svals.alloc(F.nstored);
+            F.d_svals_c.alloc(F.nstored);
+            F.sell_windowed = P.windowed;
             if (!P.perm.empty()) {
-                c->d_rperm = dalloc<int32_t>(P.perm.size());
-                HIPCHK(hipMemcpyAsync(c->d_rperm, P.perm.data(), P.perm.size() * 4, hipMemcpyHostToDevice, c->stream));
-                for (auto &v : c->d_pv) v = dalloc<double>(c->nl);
+                upload(c, F.d_rperm, P.perm);
+                for (auto &v : F.d_pv) v.alloc(c->nl);
             }
-            if (!P.sdel.empty()) {
-                c->d_sdel = dalloc<int16_t>(P.sdel.size());
-                HIPCHK(hipMemcpyAsync(c->d_sdel, P.sdel.data(), P.sdel.size() * 2, hipMemcpyHostToDevice, c->stream));
-            }
+            if (!P.sdel.empty()) upload(c, F.d_sdel, P.sdel);
             if (P.lds_rows > 0) {  // LDS-staged windows (sell_plan.cpp)
-                c->d_hptr = dalloc<int32_t>(P.hptr.size());
-                c->d_hidx = dalloc<int32_t>(std::max<size_t>(P.hidx.size(), 1));
-                c->d_sloc = dalloc<uint16_t>(P.sloc.size());
-                HIPCHK(hipMemcpyAsync(c->d_hptr, P.hptr.data(), P.hptr.size() * 4, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(hipMemcpyAsync(c->d_hidx, P.hidx.data(), P.hidx.size() * 4, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(hipMemcpyAsync(c->d_sloc, P.sloc.data(), P.sloc.size() * 2, hipMemcpyHostToDevice, c->stream));
-                c->lds_rows = P.lds_rows;
-                c->sell_lpr = P.lpr;
-                c->lds_max = P.lds_max;
-                c->lds_halo = (int64_t)P.hidx.size();
+                upload(c, F.d_hptr, P.hptr);
+                upload(c, F.d_hidx, P.hidx);
+                upload(c, F.d_sloc, P.sloc);
+                F.lds_rows = P.lds_rows;
+                F.sell_lpr = P.lpr;
+                F.lds_max = P.lds_max;
             }
             if (!P.swide.empty()) {  // mixed layout: the slices beyond 16 bits stream d_scols
-                c->d_swide = dalloc<uint8_t>(P.swide.size());
-                HIPCHK(hipMemcpyAsync(c->d_swide, P.swide.data(), P.swide.size(), hipMemcpyHostToDevice, c->stream));
-                c->sell_nnz_wide = P.nnz_wide;
+                upload(c, F.d_swide, P.swide);
+                F.sell_nnz_wide = P.nnz_wide;
             }
             HIPCHK(hipStreamSynchronize(c->stream));  // P's host buffers die at scope exit
+            static_cast<FaDeviceState &>(*c) = std::move(F);
+            if (c->lds_rows > 0) c->lds_halo = (int64_t)P.hidx.size();
         }
         // per-point coefficients at the rule of their integrator
         const size_t nqd = (size_t)c->ne * c->nq_sd, nqc = (size_t)c->ne * c->nq_scm;
-        double *dk = upload_opt(c, f->kappa_q, nqd), *dkm = upload_opt(c, f->kappa_mat_q, nqd * c->dim * (c->dim + 1) / 2);
-        double *dc = upload_opt(c, f->conv_q, nqc * c->dim), *dm = upload_opt(c, f->mass_q, nqc);
+        const DevBuf<double> dk = upload_opt(c, f->kappa_q, nqd), dkm = upload_opt(c, f->kappa_mat_q, nqd * c->dim * (c->dim + 1) / 2);
+        const DevBuf<double> dc = upload_opt(c, f->conv_q, nqc * c->dim), dm = upload_opt(c, f->mass_q, nqc);
         c->kinds = kinds;
         HIPCHK(launch_simplex_elem(c, dk, dkm, f->kappa, f->alpha, f->conv, dc, dm, f->mass));
         HIPCHK(launch_fa_assemble(c));
         HIPCHK(launch_sell_fill(c));
         HIPCHK(hipStreamSynchronize(c->stream));
-        dfree(dk); dfree(dkm); dfree(dc); dfree(dm);
         c->fa_ready = true;
         c->pa_ready = false;
         c->dinv_ready = false;
@@ -1174,11 +1080,7 @@ int cdfem_lf_assemble(cdfem_ctx *c, const double *f_q, double *b, int where)
         require_mesh(c);
         if (!f_q || !b) throw ArgError("null vector");
         const size_t n = (size_t)c->ne * (c->geom != 0 ? c->nq_lf : nq_of(c, c->rule_lf));
-        if (c->lfq_cap < n) {  // kept: a time loop assembles a linear form every step
-            dfree(c->d_lfq);
-            c->d_lfq = dalloc<double>(n);
-            c->lfq_cap = n;
-        }
+        if (c->d_lfq.size() < n) c->d_lfq.alloc(n);  // kept: a time loop assembles a linear form every step
         double *dfq = c->d_lfq;
         HIPCHK(hipMemcpyAsync(dfq, f_q, n * 8, where == CDFEM_DEVICE ? hipMemcpyDeviceToDevice
                                                                      : hipMemcpyHostToDevice, c->stream));
@@ -1268,23 +1170,21 @@ int cdfem_stream_bench(cdfem_ctx *c, int mode, size_t bytes, int reps, double *g
         if (!gbps || reps < 1 || mode < 0 || mode > 17) throw ArgError("bad stream bench arguments");
         int64_t n = (int64_t)(bytes / 16) * 2;
         if (mode >= 3) n = n / 40960 * 40960;  // whole 320 KiB chunks
-        double *a = dalloc<double>(n), *b = dalloc<double>(n);
+        DevBuf<double> a, b;
+        a.alloc(n);
+        b.alloc(n);
         HIPCHK(hipMemsetAsync(a, 0, n * 8, c->stream));
         HIPCHK(hipMemsetAsync(b, 0, n * 8, c->stream));
         HIPCHK(launch_stream(c, mode, a, b, n));  // warm-up
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
+        Event e0, e1;
+        e0.create(true);
+        e1.create(true);
         HIPCHK(hipEventRecord(e0, c->stream));
         for (int i = 0; i < reps; ++i) HIPCHK(launch_stream(c, mode, a, b, n));
         HIPCHK(hipEventRecord(e1, c->stream));
         HIPCHK(hipEventSynchronize(e1));
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        dfree(a);
-        dfree(b);
         double moved = (mode == 2 ? 2.0 : 1.0) * 8.0 * (double)n * reps;
         if (mode == 14 || mode == 15) {  // workgroup chunks: whole groups of 4 / 2 chunks
             const int64_t nw = mode == 14 ? 4 : 2;
@@ -1303,20 +1203,19 @@ int cdfem_fp64_bench(cdfem_ctx *c, int mode, int reps, double *tflops)
 {
     return guarded(c, [&] {
         if (!tflops || reps < 1 || mode < 0 || mode > 4) throw ArgError("bad fp64 bench arguments");
-        double *out = dalloc<double>(1), flops = 0.0;
+        DevBuf<double> out;
+        out.alloc(1);
+        double flops = 0.0;
         HIPCHK(launch_fp64_probe(c, mode, out, &flops));  // warm-up
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
+        Event e0, e1;
+        e0.create(true);
+        e1.create(true);
         HIPCHK(hipEventRecord(e0, c->stream));
         for (int i = 0; i < reps; ++i) HIPCHK(launch_fp64_probe(c, mode, out, &flops));
         HIPCHK(hipEventRecord(e1, c->stream));
         HIPCHK(hipEventSynchronize(e1));
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        dfree(out);
         *tflops = flops * reps / (ms * 1e-3) / 1e12;
         return CDFEM_OK;
     });

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/cdfem.h"
+#include "ctx_state.hpp"
 #include "options.hpp"
 
 namespace cdfem {
@@ -107,41 +108,80 @@ struct BcgsState {
     double red[4];                 // multi-rank: rank-local sums awaiting the all-reduce
 };
 
-// ILU(0) preconditioner state (ilu_kernels.hip)
+// A captured graph and its executable, destroyed with their owner
+struct SweepGraph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    SweepGraph() = default;
+    SweepGraph(const SweepGraph &) = delete;
+    SweepGraph &operator=(const SweepGraph &) = delete;
+    SweepGraph(SweepGraph &&o) noexcept : graph(std::exchange(o.graph, nullptr)), exec(std::exchange(o.exec, nullptr)) {}
+    SweepGraph &operator=(SweepGraph &&o) noexcept
+    {
+        std::swap(graph, o.graph);  // (o, a temporary or a state on its way out, destroys what this held)
+        std::swap(exec, o.exec);
+        return *this;
+    }
+    ~SweepGraph()
+    {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+    }
+};
+
+// ILU(0) preconditioner state (ilu_kernels.hip); ilu_free assigns a default one
 struct IluState {
     bool ready = false;
-    double *F = nullptr;                 // factors in the CSR pattern (unit-lower L, U packed)
-    int32_t *rows_l = nullptr, *rows_u = nullptr;  // rows grouped by level
+    DevBuf<double> F;                    // factors in the pattern below (unit-lower L, U packed)
+    DevBuf<int32_t> rows_l, rows_u;      // rows grouped by level
     std::vector<int32_t> ptr_l, ptr_u;   // level pointers (host)
-    double *z = nullptr;                 // output of one application
+    DevBuf<double> z;                    // output of one application
     // multi-rank (PETSc bjacobi, one ILU(0) block per rank): the factored matrix is the owned
     // diagonal block of the global eliminated matrix, on rows/columns [skip_lo, nl), in its own
     // pattern; the sweeps write the owned part of z and the owners' values are then copied to the
     // non-owned shared entries
     bool block = false;
-    int32_t *rp = nullptr, *cols = nullptr, *diag = nullptr;  // block pattern (owned; else the CSR's)
+    DevBuf<int32_t> b_rp, b_cols, b_diag;  // the block's own pattern (block only)
+    const int32_t *rp = nullptr, *cols = nullptr, *diag = nullptr;  // the pattern factored: the block's, else the CSR's
     int64_t nnz = 0;
-    hipGraph_t graph = nullptr;          // the captured forward + backward sweeps
-    hipGraphExec_t exec = nullptr;
+    SweepGraph sweeps;                   // the captured forward + backward sweeps
 };
 
 struct Comm;  // comm.hip
 
 struct ProfileSlot {
-    std::vector<hipEvent_t> ev;  // pairs
+    std::vector<Event> ev;  // pairs
     int used = 0;
     double total_ms = 0.0;
     int64_t count = 0;
     std::vector<float> each;  // per-launch ms since the last reset (cdfem_profile_launches)
 };
 
-}  // namespace cdfem
-
-// the set_option switches and their defaults are the base (options.hpp); everything else is state
-struct cdfem_ctx : cdfem::Options {
-    int device = 0;
+// The context's streams, a base of ContextState so that they are destroyed after everything the context owns
+struct Streams {
+    Streams() = default;
+    Streams(const Streams &) = delete;
+    Streams &operator=(const Streams &) = delete;
+    ~Streams()
+    {
+        if (stream2) (void)hipStreamDestroy(stream2);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
     hipStream_t stream = nullptr;
+    hipStream_t stream2 = nullptr;      // side stream of the overlapped exchange (created on first use)
+};
+
+// What lives as long as the context: the Krylov drivers' device state with its pinned slots and events, the
+// profiling slots, the communicator; and the description of the current mesh, which every upload assigns
+// before mesh_ready and everything reads behind require_mesh / require_pa.  Declared ahead of the bases
+// that own the mesh's buffers, so destroyed after them.
+struct ContextState : Streams {
+    int device = 0;
+    Event ov_ev[2];                     // fork / join of the side stream
     std::string err;
+    int ncu = 0;                        // compute units of the device
+    Comm *comm = nullptr;               // rank communicator (comm.hip), nullptr on one GPU
+    int rank = 0, nranks = 1;
 
     // mesh / space
     int dim = 0, p = 0, d1 = 0, nd = 0, ne = 0, nblk = 0, nv = 0;
@@ -149,174 +189,69 @@ struct cdfem_ctx : cdfem::Options {
                                         //    map / E-vector / qdata (wave per element, 3D p >= 3)
     int64_t nl = 0;
     int n_ess = 0;
-    bool mesh_ready = false;
-    double *d_verts = nullptr;          // [ne][nv][dim]
-    int32_t *d_map = nullptr;           // [nblk][nd][64], ess negative
-    int32_t *d_e2l_off = nullptr;       // [nl+1]
-    int32_t *d_e2l_pos = nullptr;       // [ne*nd]
-    uint8_t *d_ess = nullptr;           // [nl]
-    int32_t *d_ess_list = nullptr;      // [n_ess]
-    int32_t *d_perm = nullptr;          // [nblk*64] element at (block, lane), -1 = padding
     std::vector<int32_t> h_dofs;        // host copy of the element dof map (ne*nd)
     std::vector<uint8_t> h_ess;         // host essential marker (nl)
+    bool mesh_affine = false;           // every element a parallelepiped (checked at upload)
+    Rule1D rule_op, rule_lf, rule_err;
+    // simplex integrator rules (MFEM's GetRule on affine simplices): diffusion order 2p - 2,
+    // convection and mass order 2p, each on MFEM's tabulated rule (simplex_rule_for_order)
+    int nq_sd = 0, nq_scm = 0;          // points of the diffusion / convection + mass rules
+    int nq_lf = 0;                      // simplex LINEARFORM rule (collapsed Gauss, n = p + 3)
 
-    // structured-box fast path (cdfem_mesh_set_structured): 4x4x4-element bricks
-    bool structured = false;
-    bool epencil = false;               // qlay 1 on a structured box: pencil E-vector layout (ho_eidx)
+    // structured box (cdfem_mesh_set_structured)
     int sx = 0, sy = 0, sz = 0;         // elements per axis of the local box
     int nbx = 0, nby = 0, nbz = 0;      // bricks per axis
     // 3D p = 3, 4 on a structured box: blocks of kHoBrickEdge^3 elements for the high-order brick CG
     // (brick_kernels.hip k_hobrick_cg; set_option "ho_brick")
-    int hb_nbx = 0, hb_nby = 0, hb_nbz = 0, hb_nblk = 0;
+    int hb_nbx = 0, hb_nby = 0, hb_nbz = 0;
     int hb_ez = 2;                      //   the block depth of the current structured box
-    uint8_t *d_bess = nullptr;          // per brick (block): 1 if a dof of its patch is essential
-    double *d_hbpart = nullptr;         // den partials summed in two stages: k_hobrick_cg's, and k_brick_cg's past
-                                        // kDenFoldMaxParts bricks on one rank (one per brick)
-    double *den_out = nullptr;          // k_brick_cg writes its den partials here instead of d_part (set by the solve)
-    // grouped den partials (p <= 2 past the fold bounds: C5's per-rank slab of 32,768 bricks, its 262,144 on one
-    // GPU): the last-arriving brick of each group of den_grp sums the group's partials in a fixed order
-    // (k_brick_cg tail: write-through partial, agent-scope arrival count), so the folds sum <= 4,096 values
-    int den_grp = 1;                    // group size of the running solve (1: one partial per brick)
-    double *d_gsum = nullptr;           // [ceil(nblk / den_grp)] group sums
-    uint32_t *d_gcnt = nullptr;         // [same] arrival counters (0 between launches)
-    int64_t gsum_cap = 0;
-    double *d_uelem = nullptr;          // pa_uniform: the common element matrix in MFMA A-operand order
-    double *d_udiag = nullptr;          // [kUdiagN] the class table (setup_uniform_diag, valid while dinv_ready;
-                                        // null when the device check found d_dinv not class-constant)
-    bool udiag_bitwise = false;         //   every non-essential entry of d_dinv equals its class entry bitwise
-    double *d_hoelem = nullptr;         // ho_uniform: that matrix in MFMA A-operand order ([row tile][k step][lane],
-                                        // zero-padded to 16 x 4 multiples: 128 x 128 at p = 4)
-    int hoelem_p = 0;                   //   the order and kinds it was formed for
-    unsigned hoelem_kinds = 0;
     int64_t Lx = 0, Ly = 0, Lz = 0;     // dof lattice per axis
-    double *d_face = nullptr;           // [nblk][F] brick-face partial sums
-    double *d_ones = nullptr;           // all-ones vector (unpreconditioned brick CG)
-    double *d_dalt = nullptr;           // second search-direction buffer (brick CG)
-    int nface = 0;                      // F
-    int gm_ept_auto = 4;                // the automatic choice for vectors of gm_ept_n entries
-    int64_t gm_ept_n = -1;
-    // slab partition: the largest L-vector and brick count over all ranks (all-reduced by cdfem_set_slab),
-    // so brick_fits takes the same decision on every rank (slabs of different sizes near the
-    // bound would otherwise send ranks down CG paths with different collective sequences)
-    int64_t slab_nl_max = 0, slab_nb_max = 0;
-    int ncu = 0;                        // compute units of the device
-    int zlo_shared = 0;                 // local gz=0 plane owned by the rank below (slabs)
-    int zhi_shared = 0;                 // local gz=Lz-1 plane shared with the rank above
-    cdfem::Comm *comm = nullptr;        // rank communicator (comm.hip), nullptr on one GPU
-    int rank = 0, nranks = 1;
-    double *d_if[4] = {};               // interface planes: send_lo, recv_lo, send_hi, recv_hi
-    // rank partition of the L-vector: 0 none, 1 z-slab (cdfem_set_slab), 2 general element
-    // partition (cdfem_set_shared).  Both number the dofs owned by a lower rank first, so the
-    // owned (true) dofs are the suffix [skip_lo, nl) and every dot product skips the prefix.
-    int part_mode = 0;
-    int64_t skip_lo = 0;
-    // general partition: per neighbour rank (ascending) the shared local dofs, same order on both
-    // sides; send/recv buffers concatenated in neighbour order
-    std::vector<int32_t> nbr_rank;
-    std::vector<int64_t> nbr_off;       // [n_nbr + 1]
-    std::vector<int32_t> h_sh_idx;      // [n_sh] local dof of send/recv slot (host copy)
-    int32_t *d_sh_idx = nullptr;        // [n_sh] local dof of send/recv slot
-    double *d_sh_send = nullptr, *d_sh_recv = nullptr;
-    int32_t n_shd = 0;                  // distinct shared dofs
-    int32_t *d_shd = nullptr;           // [n_shd] their local index
-    int32_t *d_shd_off = nullptr;       // [n_shd + 1] contributions, ascending rank (own = -1)
-    int32_t *d_shd_src = nullptr;       //   source: -1 own partial, else recv slot
-    int32_t *d_shd_owner = nullptr;     // [n_shd] recv slot of the owner's copy, -1 if owned here
-
-    // rules
-    cdfem::Rule1D rule_op, rule_lf, rule_err;
-
-    // geometry family: 0 tensor (quad/hex: PA), 1 simplex (tri/tet: FA, cdfem_mesh_upload_simplex)
-    int geom = 0;
-    // simplex integrator rules (MFEM's GetRule on affine simplices): diffusion order 2p - 2,
-    // convection and mass order 2p, each on MFEM's tabulated rule (simplex_rule_for_order)
-    int nq_sd = 0, nq_scm = 0;          // points of the diffusion / convection + mass rules
-    double *d_stab = nullptr;           // rule tables, diffusion rule first then the convection + mass
-                                        // rule, each phi [nq][nd], dphi [nq][nd][dim], w [nq]
-    std::vector<double> h_verts;        // simplex host geometry (quadrature points for coefficients)
-    std::vector<double> h_sxi_d, h_sxi_cm;  // the two rules' points (reference coordinates)
-    int nq_lf = 0;                      // simplex LINEARFORM rule (collapsed Gauss, n = p + 3)
-    std::vector<double> h_sxi_lf;
-    double *d_stab_lf = nullptr;        // phi [nq_lf][nd], w [nq_lf]
-    // full assembly (cdfem_fa_setup): CSR with sorted columns + deterministic contribution lists
-    bool fa_ready = false;
-    int64_t nnz = 0;
-    int32_t *d_rowptr = nullptr, *d_cols = nullptr, *d_diagpos = nullptr;
-    int32_t *d_coff = nullptr, *d_cpos = nullptr;  // per-nonzero contribution lists into d_Ee
-    double *d_vals = nullptr;           // A
-    double *d_vals_c = nullptr;         // eliminated A (FormLinearSystem, DIAG_ONE)
-    double *d_Ee = nullptr;             // element matrices [blk][nd*nd][64]
-    int64_t nslices = 0, nstored = 0;   // SELL-64 copy (the SpMV layout)
-    int32_t *d_sptr = nullptr, *d_srows = nullptr, *d_scols = nullptr, *d_smap = nullptr;
-    double *d_tpart = nullptr;          // den partials of the fused high-order CG apply (one per tile block)
-    double *d_ktab = nullptr;           // k_apply3d_ktile's rows of M, K, C, C^T (canonical entries, [4][D1][D1])
-    double h_ktab[4 * 5 * 5] = {};      //   host copy (source of the async upload)
-    int ktab_key = -1;                  //   (p, rule) the table was built for
-    int16_t *d_sdel = nullptr;          // 16-bit column deltas (null when the bandwidth does not fit)
-    uint8_t *d_swide = nullptr;         // per slice: 1 = streams 32-bit columns (mixed layout; null: none)
-    int64_t sell_nnz_wide = 0;          // real entries in the 32-bit slices of a mixed layout
-    hipStream_t stream2 = nullptr;      // side stream of the overlapped exchange (created on first use)
-    hipEvent_t ov_ev[2] = {};           // fork / join of the side stream
-    double *d_bsum = nullptr;           // [2] cg_beta_sum: the betanom sum, then the update's arrival counter (0 between launches)
-    double *d_small = nullptr;          // a few doubles of device scratch (mr_fold_agreed's all-reduce)
-    int32_t *d_hptr = nullptr, *d_hidx = nullptr;  // LDS-staged windows (FaPattern::hptr / hidx / sloc)
-    uint16_t *d_sloc = nullptr;
-    int64_t lds_rows = 0;               // rows per window of the current LDS layout (0: none)
-    int32_t lds_max = 0;                // largest window halo (doubles)
-    int64_t lds_halo = 0;               // staged columns over all windows
-    int sell_lpr = 1;                   // lanes per row of the current SELL copy
-    int32_t *d_rperm = nullptr;         // SpMV space order: space row -> mesh row (null: mesh order)
-    bool sell_windowed = false;         // slices cut from the space order (kernel row = slice * 64 + lane)
-    double *d_pv[2] = {};               // permuted-space scratch (apply in mesh order; solve B / X)
+    int nface = 0;                      // F of d_face
+    double *den_out = nullptr;          // k_brick_cg writes its den partials here instead of d_part (set by the solve)
+    bool udiag_bitwise = false;         // d_udiag: every non-essential entry of d_dinv equals its class entry bitwise
+    int hoelem_p = 0;                   // d_hoelem: the order and kinds it was formed for
+    unsigned hoelem_kinds = 0;
+    double h_ktab[4 * 5 * 5] = {};      // d_ktab's host copy (source of the async upload)
+    int64_t lds_halo = 0;               // staged columns over all windows of the LDS layout
     bool perm_space = false;            // inside a solve that runs in the permuted order
-    double *d_dinv_p = nullptr;         // the Jacobi scale in permuted order (during such a solve)
-    double *d_svals = nullptr, *d_svals_c = nullptr;
-    cdfem::IluState ilu;                // ILU(0) of the eliminated matrix (GMRES pc = ILU)
 
-    // partial assembly
+    // the operator
     unsigned kinds = 0;
     int ncomp = 0;
-    bool pa_ready = false;
-    double *d_qd = nullptr;             // [nblk][nq][nc][64]
-    double *d_qaff = nullptr;           // [nblk][nc][64] per-element factors of an affine mesh (qd = W_q * g)
-    bool mesh_affine = false;           // every element a parallelepiped (checked at upload)
-    double *d_geom = nullptr;           // pa_geom: header + [nblk][22][64] masks and map coefficients (GeomLayout)
-    double *d_hgeom = nullptr;          // ho_geom: GeomLayout's header + [ne][24] map coefficients (HoGeomLayout)
-    double *d_Ye = nullptr;             // [nblk][nd][64]
-    double *d_dinv = nullptr;           // Jacobi (constrained: ess -> 1)
-    bool dinv_ready = false;
 
-    // work vectors (L-size)
-    double *d_w[8] = {};                // staging + Krylov vectors
-    double *d_part = nullptr;           // reduction partials [red_blocks + nblk]
+    // Krylov drivers
     int red_blocks = 1024;
-    cdfem::KrylovState *d_state = nullptr;
-    cdfem::KrylovState *h_state = nullptr;  // pinned
-    double *d_gm = nullptr;             // GMRES basis (restart+1) * nl
-    int gm_cap = 0;
-    double *d_gm_part = nullptr;        // GMRES partials [(restart+1) * blocks]
-    double *d_lfq = nullptr;            // cdfem_lf_assemble: the point values (kept across calls)
-    size_t lfq_cap = 0;
-    cdfem::GmresState *d_gmst = nullptr;   // device GMRES state
-    cdfem::GmresState *h_gmpoll = nullptr; // pinned, 2 poll slots of kGmPollBytes
-    hipEvent_t gm_ev[2] = {};
-    double *d_bcgs = nullptr;           // BiCGStab vectors x, r, rh, p, v, t (6 * padded nl), allocated by the first solve
-    int64_t bcgs_n = -1;                // the nl d_bcgs and d_bcgs_part were sized for
-    double *d_bcgs_part = nullptr;      // BiCGStab partials [3 * blocks]
-    cdfem::BcgsState *d_bcst = nullptr;    // device BiCGStab state
-    cdfem::BcgsState *h_bcpoll = nullptr;  // pinned, kBcgsSlots + 1 poll slots
-    hipEvent_t bc_ev[2] = {};
+    DevBuf<KrylovState> d_state;
+    PinBuf<KrylovState> h_state;
+    DevBuf<GmresState> d_gmst;          // device GMRES state
+    PinBuf<GmresState> h_gmpoll;        // kGmMaxRestart + 1 poll slots
+    Event gm_ev[2];
+    DevBuf<BcgsState> d_bcst;           // device BiCGStab state
+    PinBuf<BcgsState> h_bcpoll;         // kBcgsSlots + 1 poll slots
+    Event bc_ev[2];
     int last_method = -1;               // method of the last cdfem_solve (kernel_bytes / kernel_name of CDFEM_K_UPDATE)
     int bcgs_src = 0;                   // the last BiCGStab solve's operator source: 0 the Mult's output, else the patch side
     int bcgs_diag = 0;                  // the last BiCGStab solve read a Jacobi diagonal
-    int bcgs_ept_auto = 4;              // BiCGStab vector kernels' entries per thread for vectors of bcgs_ept_n entries
+    // entries per thread of the GMRES / BiCGStab vector kernels, cached for vectors of *_ept_n entries
+    int gm_ept_auto = 4;
+    int64_t gm_ept_n = -1;
+    int bcgs_ept_auto = 4;
     int64_t bcgs_ept_n = -1;
 
     // profiling
     bool profile = false;
-    cdfem::ProfileSlot prof[CDFEM_K_COUNT];
+    ProfileSlot prof[CDFEM_K_COUNT];
     hipEvent_t ext_ev[2] = {};  // armed by prof_mark(begin): the next CDFEM_LAUNCH records these
                                 // events at its own dispatch start / end (hipExtLaunchKernelGGL)
+};
+
+}  // namespace cdfem
+
+// the set_option switches and their defaults (options.hpp), then the state grouped by lifetime: the
+// context's, the uploaded mesh's and the declared partition's (ctx_state.hpp), and the ILU(0) factors of
+// the current operator and partition (ilu_free; GMRES pc = ILU)
+struct cdfem_ctx : cdfem::Options, cdfem::ContextState, cdfem::MeshState, cdfem::PartitionState {
+    cdfem::IluState ilu;
 };
 
 // Launch on the context stream; when a profiling mark is armed (prof_mark), the kernel records the
@@ -416,6 +351,9 @@ constexpr int kMrFoldMaxParts = 8192;   // cg_mr_fold: apply partials every upda
 constexpr int kDenFoldMaxParts = 16384; // cg_den_fold: beyond (C5's 256^3 on one GPU: 262,144 bricks) the
                                         // den finalizer (the update workgroups' redundant sums grow with it)
 // the Kronecker tile's x-stage table (ho_kernels.hip), built for the context's p and rule
+// (its first build allocates d_ktab.  Like setup_uniform_elem, setup_uniform_diag and setup_ho_uniform_elem
+// below, it reports a failed allocation by throwing HipError and any other failure by its return value; every
+// caller wraps the call in HIPCHK inside guarded, so both leave as CDFEM_ERR_HIP)
 hipError_t ho_ktab(cdfem_ctx *c, const double **out);
 // every buffer the brick kernels reach through a 32-bit buffer resource is below c->brick_limit bytes
 bool brick_fits(const cdfem_ctx *c);

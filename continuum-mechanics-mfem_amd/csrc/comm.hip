@@ -233,21 +233,8 @@ static void shared_pack_exchange(cdfem_ctx *c, const double *v)
 
 void partition_free(cdfem_ctx *c)
 {
-    for (int32_t **p : {&c->d_sh_idx, &c->d_shd, &c->d_shd_off, &c->d_shd_src, &c->d_shd_owner}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    for (double **p : {&c->d_sh_send, &c->d_sh_recv}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    c->nbr_rank.clear();
-    c->nbr_off.clear();
-    c->h_sh_idx.clear();
     ilu_free(c);  // a block-Jacobi factor belongs to the previous partition
-    c->n_shd = 0;
-    c->part_mode = 0;
-    c->skip_lo = 0;
+    static_cast<PartitionState &>(*c) = PartitionState{};
 }
 
 // non-owned shared entries <- the owner's value (slab: the lower plane from the rank below)

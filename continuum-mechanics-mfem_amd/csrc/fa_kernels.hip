@@ -685,8 +685,8 @@ static void spmv_launch(cdfem_ctx *c, const double *vals, const double *x, doubl
         const int spw = (int)(c->lds_rows / (64 / c->sell_lpr));
         const auto launch = [&](auto L) {
             const auto kern = k_sell_spmv_lds<CG, L()>;
-            CDFEM_LAUNCH(c, kern, g, b, (size_t)c->lds_max * sizeof(double), c->d_sptr, c->d_sloc, vals, c->d_hptr,
-                         c->d_hidx, x, y, c->nslices, (int64_t)c->nl, spw, nwin, per, part, st);
+            CDFEM_LAUNCH(c, kern, g, b, (size_t)c->lds_max * sizeof(double), c->d_sptr.get(), c->d_sloc.get(), vals, c->d_hptr.get(),
+                         c->d_hidx.get(), x, y, c->nslices, (int64_t)c->nl, spw, nwin, per, part, st);
             return true;
         };
         if (!dispatch_value<4, 2>(c->sell_lpr, false, launch)) launch(std::integral_constant<int, 1>{});
@@ -701,10 +701,10 @@ static void spmv_launch(cdfem_ctx *c, const double *vals, const double *x, doubl
         if constexpr (I16() || !MIX()) {
             using CI = std::conditional_t<I16(), int16_t, int32_t>;
             const auto kern = k_sell_spmv<CG, CI, PM(), 4, false, true, MIX()>;
-            CDFEM_LAUNCH(c, kern, g, b, 0, c->d_sptr, c->d_srows,
-                         (const CI *)(I16() ? (const void *)c->d_sdel : (const void *)c->d_scols), vals, x, y,
-                         c->nslices, (int64_t)c->nl, per, part, st, MIX() ? c->d_scols : (const int32_t *)nullptr,
-                         MIX() ? c->d_swide : (const uint8_t *)nullptr);
+            CDFEM_LAUNCH(c, kern, g, b, 0, c->d_sptr.get(), c->d_srows.get(),
+                         (const CI *)(I16() ? (const void *)c->d_sdel.get() : (const void *)c->d_scols.get()), vals, x, y,
+                         c->nslices, (int64_t)c->nl, per, part, st, MIX() ? c->d_scols.get() : (const int32_t *)nullptr,
+                         MIX() ? c->d_swide.get() : (const uint8_t *)nullptr);
         }
     });
 }

@@ -674,10 +674,7 @@ static hipError_t ktab_build(cdfem_ctx *c, const Tab<D1, Q1> &T)
     // (a rebuild follows a new setup: let any copy still reading h_ktab finish first)
     const hipError_t es = hipStreamSynchronize(c->stream);
     if (es != hipSuccess) return es;
-    if (!c->d_ktab) {
-        const hipError_t e = hipMalloc(&c->d_ktab, sizeof(c->h_ktab));
-        if (e != hipSuccess) return e;
-    }
+    if (!c->d_ktab) c->d_ktab.alloc(sizeof(c->h_ktab) / sizeof(double));
     for (int i = 0; i < D1; ++i)
         for (int j = 0; j < D1; ++j) {
             const int m = sym_can(D1, i, j), ca = anti_can(D1, i, j), sa = anti_sign(D1, i, j);
@@ -740,7 +737,7 @@ static hipError_t ktile_kinds(cdfem_ctx *c, const double *x, double *Ye, bool co
         if constexpr ((DEN() && !(CON() && LAT())) || (DF() && !DEN())) return hipErrorInvalidValue;
         else {
             const auto kern = k_apply3d_ktile<D1, Q1, K, CON(), LAT(), DEN(), DF()>;
-            CDFEM_LAUNCH(c, kern, grid, block, 0, c->d_map, x, qa, Ye, T, c->ne, geo, st, den_part,
+            CDFEM_LAUNCH(c, kern, grid, block, 0, c->d_map.get(), x, qa, Ye, T, c->ne, geo, st, den_part,
                          DF() ? dold : nullptr, DF() ? dnew : nullptr, kt);
             return hipGetLastError();
         }
@@ -776,7 +773,7 @@ static hipError_t tile_kinds_mf(cdfem_ctx *c, const double *x, double *Ye, bool 
         if constexpr (DEN() && !(CON() && LAT())) return hipErrorInvalidValue;
         else {
             const auto kern = k_apply3d_tile<D1, Q1, K, CON(), LAT(), DEN(), MF>;
-            CDFEM_LAUNCH(c, kern, grid, block, 0, c->d_map, x, qd, Ye, T, c->ne, geo, st, den_part);
+            CDFEM_LAUNCH(c, kern, grid, block, 0, c->d_map.get(), x, qd, Ye, T, c->ne, geo, st, den_part);
             return hipGetLastError();
         }
     });

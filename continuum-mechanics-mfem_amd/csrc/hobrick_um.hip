@@ -237,11 +237,11 @@ static hipError_t hobrick_um_launch(cdfem_ctx *c, const BrickGeom &g, const doub
     constexpr int NT = 64 * ((D1 * D1 * D1 + 15) / 16);
     const dim3 grid((unsigned)ho_uniform_grid(c)), block(NT);
     if (x)
-        CDFEM_LAUNCH(c, (k_hobrick_um<D1, true>), grid, block, 0, r, dinv, d_old, d_new, c->d_face, c->d_hoelem, c->d_ess,
-                     g, c->sx, c->sy, c->sz, c->d_hbpart, c->d_state, x, c->zlo_shared, c->hb_nblk);
+        CDFEM_LAUNCH(c, (k_hobrick_um<D1, true>), grid, block, 0, r, dinv, d_old, d_new, c->d_face.get(), c->d_hoelem.get(), c->d_ess.get(),
+                     g, c->sx, c->sy, c->sz, c->d_hbpart.get(), c->d_state.get(), x, c->zlo_shared, c->hb_nblk);
     else
-        CDFEM_LAUNCH(c, (k_hobrick_um<D1, false>), grid, block, 0, r, dinv, d_old, d_new, c->d_face, c->d_hoelem, c->d_ess,
-                     g, c->sx, c->sy, c->sz, c->d_hbpart, c->d_state, x, c->zlo_shared, c->hb_nblk);
+        CDFEM_LAUNCH(c, (k_hobrick_um<D1, false>), grid, block, 0, r, dinv, d_old, d_new, c->d_face.get(), c->d_hoelem.get(), c->d_ess.get(),
+                     g, c->sx, c->sy, c->sz, c->d_hbpart.get(), c->d_state.get(), x, c->zlo_shared, c->hb_nblk);
     return hipGetLastError();
 }
 
@@ -302,11 +302,7 @@ static hipError_t ho_uniform_form(cdfem_ctx *c, double *A)
 
 hipError_t setup_ho_uniform_elem(cdfem_ctx *c)
 {
-    if (c->d_hoelem) {
-        const hipError_t e = hipFree(c->d_hoelem);
-        c->d_hoelem = nullptr;
-        if (e != hipSuccess) return e;
-    }
+    c->d_hoelem.reset();
     const int q1 = c->rule_op.q1;
     // the check is taken when the 2 x 2 x 4 block CG of one rank would run on this setup (use_hobrick_cg)
     if (!c->ho_uniform || !c->structured || c->dim != 3 || c->qlay != 1 || c->pa_affine != 2 || c->d_qaff == nullptr ||
@@ -317,13 +313,12 @@ hipError_t setup_ho_uniform_elem(cdfem_ctx *c)
     c->hoelem_kinds = c->kinds;
     const int nc = c->ncomp, N = c->nd;
     // one scratch allocation: the flag, then the N x N matrix
-    void *scratch = nullptr;
-    hipError_t e = hipMalloc(&scratch, sizeof(double) * ((size_t)N * N + 1));
-    if (e != hipSuccess) return e;
-    int *bad = static_cast<int *>(scratch);
-    double *A = static_cast<double *>(scratch) + 1;
+    DevBuf<double> scratch;
+    scratch.alloc((size_t)N * N + 1);
+    int *bad = reinterpret_cast<int *>(scratch.get());
+    double *A = scratch + 1;
     int hbad = 0;
-    e = hipMemsetAsync(bad, 0, sizeof(int), c->stream);
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(int), c->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_ho_uniform_check, dim3((unsigned)((c->ne + 255) / 256)), dim3(256), 0, c->stream, c->d_qaff,
                            (int64_t)c->ne, nc, 1e-14, 1e-300, bad);
@@ -337,9 +332,7 @@ hipError_t setup_ho_uniform_elem(cdfem_ctx *c)
         if (e == hipSuccess) e = hipMemcpyAsync(h.data(), A, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     }
-    const hipError_t ef = hipFree(scratch);
     if (e != hipSuccess) return e;
-    if (ef != hipSuccess) return ef;
     if (hbad) return hipSuccess;  // not uniform: the Kronecker form
     // the A operands of v_mfma_f64_16x16x4_f64 in lane order, one row tile per wave of k_hobrick_um:
     // [mt][ks][lane] = A[16 mt + (lane & 15)][4 ks + (lane >> 4)], 0 in the padding
@@ -351,14 +344,11 @@ hipError_t setup_ho_uniform_elem(cdfem_ctx *c)
                 const int i = 16 * mt + (l & 15), j = 4 * ks + (l >> 4);
                 if (i < N && j < N) op[((size_t)mt * KS + ks) * 64 + l] = h[(size_t)i * N + j];
             }
-    void *d = nullptr;
-    if ((e = hipMalloc(&d, sizeof(double) * op.size())) != hipSuccess) return e;
+    DevBuf<double> d;
+    d.alloc(op.size());
     e = hipMemcpy(d, op.data(), sizeof(double) * op.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return e;
-    }
-    c->d_hoelem = static_cast<double *>(d);
+    if (e != hipSuccess) return e;
+    c->d_hoelem = std::move(d);
     return hipSuccess;
 }
 

@@ -1,11 +1,12 @@
 // host_util.hpp — host-side utilities of the library: the typed errors and their mapping to the C-ABI's
-// return codes, checked HIP calls, device allocation, and the profiling marks.
+// return codes, checked HIP calls, uploads into the owning buffers of handles.hpp, and the profiling marks.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <new>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "cdfem_internal.hpp"
 
@@ -50,20 +51,19 @@ int guarded(cdfem_ctx *c, F &&f)
     }
 }
 
-template <typename T>
-void dfree(T *&p)
+// b <- n elements of host memory: allocated (what it held is freed first) and copied on the context stream.
+// The source must stay alive until the stream has been synchronised.
+template <typename T, typename Mem>
+void upload(cdfem_ctx *c, Buf<T, Mem> &b, const T *src, size_t n)
 {
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
+    b.assign(src, n, [c](void *dst, const void *s, size_t bytes) {
+        HIPCHK(hipMemcpyAsync(dst, s, bytes, hipMemcpyHostToDevice, c->stream));
+    });
 }
-
-template <typename T>
-T *dalloc(size_t n)
+template <typename T, typename Mem>
+void upload(cdfem_ctx *c, Buf<T, Mem> &b, const std::vector<T> &v)
 {
-    void *p = nullptr;
-    if (n == 0) n = 1;
-    HIPCHK(hipMalloc(&p, n * sizeof(T)));
-    return static_cast<T *>(p);
+    upload(c, b, v.data(), v.size());
 }
 
 // ---- profiling (capi.hip) -------------------------------------------------------------------------

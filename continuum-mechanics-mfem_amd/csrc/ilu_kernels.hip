@@ -115,15 +115,7 @@ static void level_sets(const std::vector<int32_t> &rp, const std::vector<int32_t
 
 void ilu_free(cdfem_ctx *c)
 {
-    auto &u = c->ilu;
-    if (u.exec) (void)hipGraphExecDestroy(u.exec);
-    if (u.graph) (void)hipGraphDestroy(u.graph);
-    for (void *p : {(void *)u.F, (void *)u.rows_l, (void *)u.rows_u, (void *)u.z})
-        if (p) (void)hipFree(p);
-    if (u.block)
-        for (void *p : {(void *)u.rp, (void *)u.cols, (void *)u.diag})
-            if (p) (void)hipFree(p);
-    u = IluState{};
+    c->ilu = IluState{};
 }
 
 static void chk(hipError_t e)
@@ -168,29 +160,25 @@ static void build_owned_block(cdfem_ctx *c, const std::vector<int32_t> &rp, cons
     for (int k = 0; k <= nn; ++k) off1[k] = k;
     std::vector<double> cnt_send(nn), cnt_recv(nn);
     for (int k = 0; k < nn; ++k) cnt_send[k] = (double)out[k].size();
-    double *d_a = nullptr, *d_b = nullptr;
-    chk(hipMalloc(&d_a, std::max(nn, 1) * sizeof(double)));
-    chk(hipMalloc(&d_b, std::max(nn, 1) * sizeof(double)));
+    DevBuf<double> d_a, d_b;
+    d_a.alloc(nn);
+    d_b.alloc(nn);
     chk(hipMemcpyAsync(d_a, cnt_send.data(), nn * sizeof(double), hipMemcpyHostToDevice, c->stream));
     comm_exchange_nbr_buf(c, off1, d_a, d_b);
     chk(hipMemcpyAsync(cnt_recv.data(), d_b, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     chk(hipStreamSynchronize(c->stream));
-    (void)hipFree(d_a);
-    (void)hipFree(d_b);
     std::vector<int64_t> off2(nn + 1, 0);
     for (int k = 0; k < nn; ++k)
         off2[k + 1] = off2[k] + std::max((int64_t)cnt_send[k], (int64_t)cnt_recv[k]);
     const int64_t tot = off2[nn];
     std::vector<double> hs(tot, 0.0), hr(tot, 0.0);
     for (int k = 0; k < nn; ++k) std::copy(out[k].begin(), out[k].end(), hs.begin() + off2[k]);
-    chk(hipMalloc(&d_a, std::max<int64_t>(tot, 1) * sizeof(double)));
-    chk(hipMalloc(&d_b, std::max<int64_t>(tot, 1) * sizeof(double)));
+    d_a.alloc(tot);
+    d_b.alloc(tot);
     chk(hipMemcpyAsync(d_a, hs.data(), tot * sizeof(double), hipMemcpyHostToDevice, c->stream));
     comm_exchange_nbr_buf(c, off2, d_a, d_b);
     chk(hipMemcpyAsync(hr.data(), d_b, tot * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     chk(hipStreamSynchronize(c->stream));
-    (void)hipFree(d_a);
-    (void)hipFree(d_b);
     // rows of the block: (column, value) in summation order, then merged per column
     std::vector<std::vector<std::pair<int32_t, double>>> row(no);
     for (int64_t i = lo; i < n; ++i)
@@ -230,7 +218,19 @@ static void build_owned_block(cdfem_ctx *c, const std::vector<int32_t> &rp, cons
 // factor the eliminated matrix (values d_vals_c, pattern d_rowptr / d_cols; on several ranks the
 // owned diagonal block, build_owned_block) once per operator and capture the sweep graph:
 // in = c->d_w[4] (the GMRES work vector), out = u.z
+static void ilu_setup_once(cdfem_ctx *c);
 void ilu_setup(cdfem_ctx *c)
+{
+    // every failure of the setup leaves as a std::runtime_error, an allocation's HipError included (the
+    // status code it always had)
+    try {
+        ilu_setup_once(c);
+    } catch (const std::runtime_error &e) {
+        throw std::runtime_error(e.what());
+    }
+}
+
+static void ilu_setup_once(cdfem_ctx *c)
 {
     if (c->ilu.ready) return;
     ilu_free(c);
@@ -258,20 +258,22 @@ void ilu_setup(cdfem_ctx *c)
             if (bdiag[i] < 0) throw std::runtime_error("ILU setup: owned block row without a diagonal entry");
         u.block = true;
         u.nnz = (int64_t)bcols.size();
-        chk(hipMalloc(&u.rp, (nb + 1) * 4));
-        chk(hipMalloc(&u.cols, std::max<int64_t>(u.nnz, 1) * 4));
-        chk(hipMalloc(&u.diag, std::max<int64_t>(nb, 1) * 4));
-        chk(hipMalloc(&u.F, std::max<int64_t>(u.nnz, 1) * sizeof(double)));
-        chk(hipMemcpyAsync(u.rp, brp.data(), (nb + 1) * 4, hipMemcpyHostToDevice, c->stream));
-        chk(hipMemcpyAsync(u.cols, bcols.data(), u.nnz * 4, hipMemcpyHostToDevice, c->stream));
-        chk(hipMemcpyAsync(u.diag, bdiag.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
-        chk(hipMemcpyAsync(u.F, bvals.data(), u.nnz * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        const auto copy = [c](void *dst, const void *src, size_t bytes) {
+            chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+        };
+        u.b_rp.assign(brp, copy);
+        u.b_cols.assign(bcols, copy);
+        u.b_diag.assign(bdiag, copy);
+        u.F.assign(bvals, copy);
+        u.rp = u.b_rp;
+        u.cols = u.b_cols;
+        u.diag = u.b_diag;
     } else {
         u.rp = c->d_rowptr;
         u.cols = c->d_cols;
         u.diag = c->d_diagpos;
         u.nnz = c->nnz;
-        chk(hipMalloc(&u.F, c->nnz * sizeof(double)));
+        u.F.alloc(c->nnz);
         chk(hipMemcpyAsync(u.F, c->d_vals_c, c->nnz * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     }
     const std::vector<int32_t> &prp = block ? brp : rp;
@@ -279,9 +281,9 @@ void ilu_setup(cdfem_ctx *c)
     std::vector<int32_t> rows_l, rows_u;
     level_sets(prp, pcols, nb, true, rows_l, u.ptr_l);
     level_sets(prp, pcols, nb, false, rows_u, u.ptr_u);
-    chk(hipMalloc(&u.rows_l, std::max<int64_t>(nb, 1) * 4));
-    chk(hipMalloc(&u.rows_u, std::max<int64_t>(nb, 1) * 4));
-    chk(hipMalloc(&u.z, n * sizeof(double)));
+    u.rows_l.alloc(nb);
+    u.rows_u.alloc(nb);
+    u.z.alloc(n);
     chk(hipMemsetAsync(u.z, 0, n * sizeof(double), c->stream));
     chk(hipMemcpyAsync(u.rows_l, rows_l.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
     chk(hipMemcpyAsync(u.rows_u, rows_u.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
@@ -306,8 +308,8 @@ void ilu_setup(cdfem_ctx *c)
         hipLaunchKernelGGL(k_ilu_upper_level, dim3((cnt + 255) / 256), dim3(256), 0, c->stream, u.rp, u.cols, u.diag,
                            u.F, u.rows_u + u.ptr_u[l], cnt, z);
     }
-    chk(hipStreamEndCapture(c->stream, &u.graph));
-    chk(hipGraphInstantiate(&u.exec, u.graph, nullptr, nullptr, 0));
+    chk(hipStreamEndCapture(c->stream, &u.sweeps.graph));
+    chk(hipGraphInstantiate(&u.sweeps.exec, u.sweeps.graph, nullptr, nullptr, 0));
     chk(hipStreamSynchronize(c->stream));
     u.ready = true;
 }
@@ -316,7 +318,7 @@ void ilu_setup(cdfem_ctx *c)
 // shared entries take their owner's value), so z is a consistent L-vector like a Jacobi product
 hipError_t ilu_apply(cdfem_ctx *c)
 {
-    const hipError_t e = hipGraphLaunch(c->ilu.exec, c->stream);
+    const hipError_t e = hipGraphLaunch(c->ilu.sweeps.exec, c->stream);
     if (e != hipSuccess || !c->ilu.block) return e;
     interface_copy_owner(c, c->ilu.z);
     return hipGetLastError();

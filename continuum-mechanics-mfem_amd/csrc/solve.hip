@@ -72,7 +72,7 @@ namespace {
 // n <= 8 host doubles summed over the ranks in place: staged through d_small, read back, stream idle after
 void host_allreduce(cdfem_ctx *c, double *h, int n)
 {
-    if (!c->d_small) c->d_small = dalloc<double>(8);
+    if (!c->d_small) c->d_small.alloc(8);
     HIPCHK(hipMemcpyAsync(c->d_small, h, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     comm_allreduce(c, c->d_small, n);
     HIPCHK(hipMemcpyAsync(h, c->d_small, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -84,9 +84,8 @@ using Clock = std::chrono::steady_clock;
 const double *ones_vector(cdfem_ctx *c)
 {
     if (!c->d_ones) {
-        c->d_ones = dalloc<double>(c->nl);
-        std::vector<double> one(c->nl, 1.0);
-        HIPCHK(hipMemcpyAsync(c->d_ones, one.data(), c->nl * 8, hipMemcpyHostToDevice, c->stream));
+        const std::vector<double> one(c->nl, 1.0);
+        upload(c, c->d_ones, one);
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     return c->d_ones;
@@ -97,7 +96,7 @@ const double *solver_dinv(cdfem_ctx *c)
 {
     ensure_dinv(c);
     if (!c->perm_space) return c->d_dinv;
-    if (!c->d_dinv_p) c->d_dinv_p = dalloc<double>(c->nl);
+    if (!c->d_dinv_p) c->d_dinv_p.alloc(c->nl);
     HIPCHK(launch_perm(c, true, c->d_dinv, c->d_dinv_p));
     return c->d_dinv_p;
 }
@@ -204,17 +203,17 @@ void patch_mult_phase1(cdfem_ctx *c, const double *u, double *w)
 void solve_cg_brick(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, double *dX, cdfem_solver_result &res)
 {
     double *x = c->d_w[2], *r = c->d_w[3], *q = c->d_w[4];
-    if (!c->d_dalt) c->d_dalt = dalloc<double>(c->nl);
+    if (!c->d_dalt) c->d_dalt.alloc(c->nl);
     const int nbrick = brick_count(c);
     if (!c->d_face) {  // (p = 3, 4: the blocks' patch buffer, first use)
         const int S = brick_patch_side(c), SZ = brick_patch_side_z(c);
-        c->d_face = dalloc<double>((size_t)nbrick * S * S * SZ);
+        c->d_face.alloc((size_t)nbrick * S * S * SZ);
     }
     // the apply's den partials in two stages (a block per 1/256 of them, then one block) when the one
     // block finalizer would sum too many: the p = 3, 4 blocks, and one rank past the den fold's bound
     const int ndp = den_parts(c);  // the den partials the folds sum (grouped past the bounds: den_group)
     const bool two_stage = c->p >= 3 || (!multi_rank(c) && ndp > kDenFoldMaxParts);
-    if (two_stage && !c->d_hbpart) c->d_hbpart = dalloc<double>(nbrick);
+    if (two_stage && !c->d_hbpart) c->d_hbpart.alloc(nbrick);
     c->den_out = two_stage && c->p <= 2 ? c->d_hbpart : nullptr;
     struct DenOutReset {
         cdfem_ctx *c;
@@ -240,7 +239,7 @@ void solve_cg_brick(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB
     const bool overlap = mr && c->mr_overlap && !c->profile && c->p <= 2 && c->nbz >= 3;
     if (overlap && !c->stream2) {
         HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-        for (auto &e : c->ov_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (auto &e : c->ov_ev) e.create(false);
     }
     // x-fold (set_option "cg_xfold", default): every apply after the first advances x by the previous
     // iteration's alpha d (the update kernel then streams neither x nor d); k_cg_xflush adds the
@@ -255,18 +254,15 @@ void solve_cg_brick(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB
     const bool bfold = mr ? mrfold : cg_beta_fold_ok(c);
     // grouped den partials: taken when a fold sums them (several ranks: the fold; one rank: the den fold)
     const int grp = (mr ? mrfold : (!two_stage && cg_den_fold_on(c))) ? den_group(c) : 1;
-    if (grp > 1 && c->gsum_cap < ndp) {
-        dfree(c->d_gsum);
-        dfree(c->d_gcnt);
-        c->d_gsum = dalloc<double>(ndp);
-        c->d_gcnt = dalloc<uint32_t>(ndp);
+    if (grp > 1 && c->d_gsum.size() < (size_t)ndp) {
+        c->d_gsum.alloc(ndp);
+        c->d_gcnt.alloc(ndp);
         HIPCHK(hipMemsetAsync(c->d_gcnt, 0, (size_t)ndp * sizeof(uint32_t), c->stream));
-        c->gsum_cap = ndp;
     }
     c->den_grp = grp;
     // cg_beta_sum: the betanom sum and the update's arrival counter (zeroed once: the last arriver resets it)
     if (!mr && bfold && !c->d_bsum) {
-        c->d_bsum = dalloc<double>(2);
+        c->d_bsum.alloc(2);
         HIPCHK(hipMemsetAsync(c->d_bsum, 0, 2 * sizeof(double), c->stream));
     }
     double *const dparts = grp > 1 ? c->d_gsum : c->d_part;  // what the mr fold all-reduces (ndp of them)
@@ -349,10 +345,10 @@ void solve_cg(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, doub
     // update (ho_kernels.hip k_apply3d_tile<DEN>, vec_kernels.hip k_e2l_box<UPD>)
     const bool fused = !mr && !c->fa_ready && c->cg_fused && tile_den_ok(c) && e2l_box_ok(c) &&
                        c->nl < ((int64_t)1 << 31);  // the flat update's fast division is exact below 2^31
-    if (fused && !c->d_tpart) c->d_tpart = dalloc<double>(tile_den_blocks(c, true));
+    if (fused && !c->d_tpart) c->d_tpart.alloc(tile_den_blocks(c, true));
     // direction fold (ho_dfold): apply j forms d_j = z + beta d_{j-1} into the other direction buffer
     const bool dfold = fused && tile_dfold_ok(c);
-    if (dfold && !c->d_dalt) c->d_dalt = dalloc<double>(c->nl);
+    if (dfold && !c->d_dalt) c->d_dalt.alloc(c->nl);
     double *dprev = d, *dcur = dfold ? c->d_dalt : d;
     const auto t0 = solve_begin(c);
     cg_start(c, p, dB, x, r, z, d, dinv);
@@ -418,19 +414,16 @@ void solve_gmres(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, d
     const int64_t n = c->nl;
     const int64_t ldv = padded_ld(n);
     const int nb = gmres_blocks(n);
-    if (c->gm_cap < m) {
-        dfree(c->d_gm);
-        dfree(c->d_gm_part);
-        c->d_gm = dalloc<double>((size_t)(m + 1) * ldv);
-        c->d_gm_part = dalloc<double>((size_t)(m + 1) * nb);
-        c->gm_cap = m;
+    if (c->d_gm.size() < (size_t)(m + 1) * ldv) {  // (the first solve of this mesh, or a longer restart)
+        c->d_gm.alloc((size_t)(m + 1) * ldv);
+        c->d_gm_part.alloc((size_t)(m + 1) * nb);
     }
     if (!c->d_gmst) {
-        HIPCHK(hipMalloc(&c->d_gmst, sizeof(GmresState)));
+        c->d_gmst.alloc(1);
         // poll slots: 0 for the cycle start / end, 1 + j for inner step j (each step its own slot, so a
         // host check reads exactly the state of the step it waited for: ranks decide alike)
-        HIPCHK(hipHostMalloc(&c->h_gmpoll, (kGmMaxRestart + 1) * sizeof(GmresState), hipHostMallocDefault));
-        for (auto &e : c->gm_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->h_gmpoll.alloc(kGmMaxRestart + 1);
+        for (auto &e : c->gm_ev) e.create(false);
     }
     const bool ilu = p.pc == CDFEM_PC_ILU;
     const double *dinv = resolve_pc(c, p);
@@ -534,17 +527,14 @@ void solve_bicgstab(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB
     const int64_t n = c->nl;
     const int64_t ldv = padded_ld(n);
     const int nb = bcgs_blocks(n);
-    if (c->bcgs_n != n || !c->d_bcgs) {
-        dfree(c->d_bcgs);
-        dfree(c->d_bcgs_part);
-        c->d_bcgs = dalloc<double>((size_t)6 * ldv);
-        c->d_bcgs_part = dalloc<double>((size_t)3 * nb);
-        c->bcgs_n = n;
+    if (!c->d_bcgs) {  // (the first BiCGStab solve of this mesh)
+        c->d_bcgs.alloc((size_t)6 * ldv);
+        c->d_bcgs_part.alloc((size_t)3 * nb);
     }
     if (!c->d_bcst) {
-        HIPCHK(hipMalloc(&c->d_bcst, sizeof(BcgsState)));
-        HIPCHK(hipHostMalloc(&c->h_bcpoll, (kBcgsSlots + 1) * sizeof(BcgsState), hipHostMallocDefault));
-        for (auto &e : c->bc_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->d_bcst.alloc(1);
+        c->h_bcpoll.alloc(kBcgsSlots + 1);
+        for (auto &e : c->bc_ev) e.create(false);
     }
     const bool ilu = p.pc == CDFEM_PC_ILU;
     const double *dinv = resolve_pc(c, p);
@@ -641,7 +631,7 @@ void ensure_dinv(cdfem_ctx *c)
     if (multi_rank(c)) {
         double all = c->d_udiag ? 1.0 : 0.0;
         host_allreduce(c, &all, 1);
-        if (all != (double)c->nranks) dfree(c->d_udiag);
+        if (all != (double)c->nranks) c->d_udiag.reset();
     }
     c->dinv_ready = true;
 }
