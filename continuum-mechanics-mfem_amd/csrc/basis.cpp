@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cmath>
 #include <stdexcept>
+#include <type_traits>
 #include <vector>
 
 #include "cdfem_internal.hpp"
@@ -209,62 +210,91 @@ int simplex_ndofs(int dim, int p)
 // matrix, formed once.
 double p3_edge_t(int k) { return k == 0 ? 0.5 * (1.0 - 1.0 / std::sqrt(5.0)) : 0.5 * (1.0 + 1.0 / std::sqrt(5.0)); }
 
-void p3_tri_nodes(double (*X)[2])
+// The P3 machinery in the scalar type T: double for the tables of the linear forms (simplex_basis), long double
+// for simplex_basis_x, whose values are rounded to double once at the end.
+template <class T>
+static void p3_tri_nodes_t(T (*X)[2])
 {
-    const double V[3][2] = {{0, 0}, {1, 0}, {0, 1}};
+    const T V[3][2] = {{0, 0}, {1, 0}, {0, 1}};
     for (int v = 0; v < 3; ++v) { X[v][0] = V[v][0]; X[v][1] = V[v][1]; }
     for (int e = 0; e < 3; ++e)
         for (int k = 0; k < 2; ++k) {
             const int a = kTriEdge[e][0], b = kTriEdge[e][1];
-            const double t = p3_edge_t(k);
+            T t;
+            if constexpr (std::is_same_v<T, double>) t = p3_edge_t(k);
+            else t = (T(1) + (k == 0 ? T(-1) : T(1)) / std::sqrt(T(5))) / T(2);
             for (int d = 0; d < 2; ++d) X[3 + 2 * e + k][d] = V[a][d] + t * (V[b][d] - V[a][d]);
         }
-    X[9][0] = X[9][1] = 1.0 / 3.0;
+    X[9][0] = X[9][1] = T(1) / T(3);
 }
 
-static void p3_monomials(const double *x, double *m, double *mx, double *my)
+void p3_tri_nodes(double (*X)[2]) { p3_tri_nodes_t<double>(X); }
+
+template <class T>
+static void p3_monomials(const T *x, T *m, T *mx, T *my)
 {
     int k = 0;
     for (int tot = 0; tot <= 3; ++tot)
         for (int j = 0; j <= tot; ++j, ++k) {
             const int i = tot - j;  // x^i y^j
             m[k] = std::pow(x[0], i) * std::pow(x[1], j);
-            mx[k] = i > 0 ? i * std::pow(x[0], i - 1) * std::pow(x[1], j) : 0.0;
-            my[k] = j > 0 ? j * std::pow(x[0], i) * std::pow(x[1], j - 1) : 0.0;
+            mx[k] = i > 0 ? i * std::pow(x[0], i - 1) * std::pow(x[1], j) : T(0);
+            my[k] = j > 0 ? j * std::pow(x[0], i) * std::pow(x[1], j - 1) : T(0);
         }
 }
 
-static const std::vector<double> &p3_coeffs()
+template <class T>
+static const std::vector<T> &p3_coeffs()
 {
-    static const std::vector<double> C = [] {
-        double X[10][2];
-        p3_tri_nodes(X);
-        double A[10][20] = {};
+    static const std::vector<T> C = [] {
+        T X[10][2];
+        p3_tri_nodes_t<T>(X);
+        T A[10][20] = {};
         for (int r = 0; r < 10; ++r) {  // V[r][c] = m_c(node_r), augmented with I
-            double m[10], mx[10], my[10];
-            p3_monomials(X[r], m, mx, my);
+            T m[10], mx[10], my[10];
+            p3_monomials<T>(X[r], m, mx, my);
             for (int c = 0; c < 10; ++c) A[r][c] = m[c];
-            A[r][10 + r] = 1.0;
+            A[r][10 + r] = T(1);
         }
         for (int c = 0; c < 10; ++c) {  // Gauss-Jordan, partial pivoting
             int piv = c;
             for (int r = c + 1; r < 10; ++r)
                 if (std::fabs(A[r][c]) > std::fabs(A[piv][c])) piv = r;
             for (int k = 0; k < 20; ++k) std::swap(A[c][k], A[piv][k]);
-            const double d = A[c][c];
+            const T d = A[c][c];
             for (int k = 0; k < 20; ++k) A[c][k] /= d;
             for (int r = 0; r < 10; ++r)
                 if (r != c) {
-                    const double f = A[r][c];
+                    const T f = A[r][c];
                     for (int k = 0; k < 20; ++k) A[r][k] -= f * A[c][k];
                 }
         }
-        std::vector<double> out(100);  // out[c * 10 + i] = (V^-1)[c][i]: phi_i = sum_c m_c out[c][i]
+        std::vector<T> out(100);  // out[c * 10 + i] = (V^-1)[c][i]: phi_i = sum_c m_c out[c][i]
         for (int c = 0; c < 10; ++c)
             for (int i = 0; i < 10; ++i) out[c * 10 + i] = A[c][10 + i];
         return out;
     }();
     return C;
+}
+
+template <class T>
+static void p3_basis(const double *xi, double *phi, double *dphi)
+{
+    const std::vector<T> &C = p3_coeffs<T>();
+    const T x[2] = {T(xi[0]), T(xi[1])};
+    T m[10], mx[10], my[10];
+    p3_monomials<T>(x, m, mx, my);
+    for (int i = 0; i < 10; ++i) {
+        T v = 0, gx = 0, gy = 0;
+        for (int c = 0; c < 10; ++c) {
+            v += m[c] * C[c * 10 + i];
+            gx += mx[c] * C[c * 10 + i];
+            gy += my[c] * C[c * 10 + i];
+        }
+        phi[i] = (double)v;
+        dphi[i * 2] = (double)gx;
+        dphi[i * 2 + 1] = (double)gy;
+    }
 }
 
 // Local order: vertices, then edges (0,1),(0,2),(0,3),(1,2),(1,3),(2,3) [2D (0,1),(0,2),(1,2)].
@@ -274,20 +304,7 @@ const int kTriEdge[3][2] = {{0, 1}, {0, 2}, {1, 2}};
 void simplex_basis(int dim, int p, const double *xi, double *phi, double *dphi)
 {
     if (dim == 2 && p == 3) {
-        const std::vector<double> &C = p3_coeffs();
-        double m[10], mx[10], my[10];
-        p3_monomials(xi, m, mx, my);
-        for (int i = 0; i < 10; ++i) {
-            double v = 0.0, gx = 0.0, gy = 0.0;
-            for (int c = 0; c < 10; ++c) {
-                v += m[c] * C[c * 10 + i];
-                gx += mx[c] * C[c * 10 + i];
-                gy += my[c] * C[c * 10 + i];
-            }
-            phi[i] = v;
-            dphi[i * 2] = gx;
-            dphi[i * 2 + 1] = gy;
-        }
+        p3_basis<double>(xi, phi, dphi);
         return;
     }
     double lam[4], dl[4][3] = {};
@@ -312,6 +329,16 @@ void simplex_basis(int dim, int p, const double *xi, double *phi, double *dphi)
         phi[l] = 4.0 * lam[a] * lam[b];
         for (int k = 0; k < dim; ++k) dphi[l * dim + k] = 4.0 * (lam[a] * dl[b][k] + lam[b] * dl[a][k]);
     }
+}
+
+// The same basis with the P3 tables formed in long double and rounded once (1 ulp instead of the 1e-14 of the
+// double Vandermonde inverse).  For forms that interpolate a state from its nodal values: grad u = sum_i u_i grad
+// phi_i cancels the state's constant part, so a table error d becomes a relative error d |u| / (h |grad u|) of
+// grad u, 1e-12 of the nonlinear residual on the reference's unit square at P3.  P1 and P2 are closed formulas.
+void simplex_basis_x(int dim, int p, const double *xi, double *phi, double *dphi)
+{
+    if (dim == 2 && p == 3) p3_basis<long double>(xi, phi, dphi);
+    else simplex_basis(dim, p, xi, phi, dphi);
 }
 
 }  // namespace cdfem

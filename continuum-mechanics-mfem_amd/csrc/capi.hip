@@ -190,6 +190,11 @@ void build_layout(cdfem_ctx *c, const std::vector<int32_t> &perm)
     HIPCHK(hipStreamSynchronize(c->stream));
 }
 
+}  // namespace
+
+// ---- call-order checks and the copy-in / copy-out helpers of the entry points (host_util.hpp) ----
+namespace cdfem {
+
 void require_mesh(cdfem_ctx *c)
 {
     if (!c->mesh_ready) throw StateError("cdfem_mesh_upload has not been called");
@@ -238,8 +243,80 @@ void dev_out(cdfem_ctx *c, double *dst, int where, const double *dsrc, size_t n)
     HIPCHK(hipStreamSynchronize(c->stream));
 }
 
+// the assembled operator's CSR pattern, contribution lists and SELL copy on the device: once per mesh
+void fa_ensure_pattern(cdfem_ctx *c)
+{
+    if (c->d_rowptr) return;
+    // a multi-rank partition keeps the mesh order (its shared-dof exchange indexes L-vectors)
+    // dof coordinates for the geometric SpMV order (simplex geometry is on the host)
+    std::vector<double> xyz;
+    if (!multi_rank(c) && (c->sell_mode == 3 || c->sell_mode >= 5) && !c->h_verts.empty())
+        xyz = simplex_dof_coords(c->dim, c->p, c->ne, c->nd, c->nl, c->h_verts, c->h_dofs);
+    FaPattern P = fa_build_pattern(c->h_dofs, c->ne, c->nd, c->nl,
+                                   multi_rank(c) ? 0 : c->sell_mode, c->dim,
+                                   xyz.empty() ? nullptr : xyz.data(), c->sell_window, c->spmv_lds,
+                                   c->spmv_lpr);
+    if (P.lds_rows > 0) {
+        // the LDS-staged SpMV launches one block per window (rounded up to whole XCD ranges)
+        // and its CG form writes one partial per block: the grid must fit the partial slots
+        // (ADVICE r03).  Windows halve below their nominal size when halos are large, so the
+        // automatic choice falls back to the layout without LDS; an explicit one is refused.
+        const int64_t spw = P.lds_rows / (kLanes / std::max(1, P.lpr));
+        const int64_t nwin = ((int64_t)P.sptr.size() - 1 + spw - 1) / spw;
+        if (8 * ((nwin + 7) / 8) > kSpmvMaxBlocks) {
+            if (c->spmv_lds >= 0)
+                throw UnsupportedError("spmv_lds " + std::to_string(c->spmv_lds) + ": " +
+                                       std::to_string(nwin) + " LDS windows exceed the SpMV grid (" +
+                                       std::to_string(kSpmvMaxBlocks) + " blocks); use larger windows or 0");
+            P = fa_build_pattern(c->h_dofs, c->ne, c->nd, c->nl, multi_rank(c) ? 0 : c->sell_mode,
+                                 c->dim, xyz.empty() ? nullptr : xyz.data(), c->sell_window, 0, 1);
+        }
+    }
+    const int64_t nslices = (int64_t)P.sptr.size() - 1;
+    if ((nslices + 3) / 4 + 8 > kSpmvMaxBlocks) throw UnsupportedError("matrix too large for the SpMV grid");
+    // built aside and moved into the context whole, after the last call that can throw
+    FaDeviceState F;
+    F.nnz = P.nnz;
+    upload(c, F.d_rowptr, P.rowptr);
+    upload(c, F.d_cols, P.cols);
+    upload(c, F.d_diagpos, P.diagpos);
+    upload(c, F.d_coff, P.coff);
+    upload(c, F.d_cpos, P.cpos);
+    F.d_vals.alloc(F.nnz);
+    F.d_vals_c.alloc(F.nnz);
+    F.d_Ee.alloc((size_t)c->nblk * c->nd * c->nd * kLanes);
+    F.nslices = nslices;
+    F.nstored = P.sptr.back();
+    upload(c, F.d_sptr, P.sptr);
+    upload(c, F.d_srows, P.srows);
+    upload(c, F.d_scols, P.scols);
+    upload(c, F.d_smap, P.smap);
+    F.d_svals.alloc(F.nstored);
+    F.d_svals_c.alloc(F.nstored);
+    F.sell_windowed = P.windowed;
+    if (!P.perm.empty()) {
+        upload(c, F.d_rperm, P.perm);
+        for (auto &v : F.d_pv) v.alloc(c->nl);
+    }
+    if (!P.sdel.empty()) upload(c, F.d_sdel, P.sdel);
+    if (P.lds_rows > 0) {  // LDS-staged windows (sell_plan.cpp)
+        upload(c, F.d_hptr, P.hptr);
+        upload(c, F.d_hidx, P.hidx);
+        upload(c, F.d_sloc, P.sloc);
+        F.lds_rows = P.lds_rows;
+        F.sell_lpr = P.lpr;
+        F.lds_max = P.lds_max;
+    }
+    if (!P.swide.empty()) {  // mixed layout: the slices beyond 16 bits stream d_scols
+        upload(c, F.d_swide, P.swide);
+        F.sell_nnz_wide = P.nnz_wide;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));  // P's host buffers die at scope exit
+    static_cast<FaDeviceState &>(*c) = std::move(F);
+    if (c->lds_rows > 0) c->lds_halo = (int64_t)P.hidx.size();
+}
 
-}  // namespace
+}  // namespace cdfem
 
 // ================================================================================================
 extern "C" {
@@ -678,6 +755,11 @@ static int simplex_rule_pts(const cdfem_ctx *c, int rule, const std::vector<doub
     case CDFEM_RULE_CONVECTION:
     case CDFEM_RULE_MASS: x = &c->h_sxi_cm; nq = c->nq_scm; break;
     case CDFEM_RULE_LINEARFORM: x = &c->h_sxi_lf; nq = c->nq_lf; break;
+    case CDFEM_RULE_NONLINEAR:
+        if (!c->heat.ready) throw StateError("CDFEM_RULE_NONLINEAR: cdfem_nl_setup has not been called");
+        x = &c->heat.h_sxi;
+        nq = c->heat.nq;
+        break;
     case CDFEM_RULE_OPERATOR:
         throw UnsupportedError("simplex meshes: each integrator has its own rule (CDFEM_RULE_DIFFUSION, "
                                "CDFEM_RULE_CONVECTION, CDFEM_RULE_MASS)");
@@ -940,75 +1022,7 @@ static int fa_setup_form(cdfem_ctx *c, const cdfem_form_coeffs *f)
         check_form(c, f);
         const unsigned kinds = f->kinds;
         if (c->geom != 1) throw UnsupportedError("full assembly is implemented for simplex meshes");
-        if (!c->d_rowptr) {  // CSR pattern + contribution lists: once per mesh
-            // a multi-rank partition keeps the mesh order (its shared-dof exchange indexes L-vectors)
-            // dof coordinates for the geometric SpMV order (simplex geometry is on the host)
-            std::vector<double> xyz;
-            if (!multi_rank(c) && (c->sell_mode == 3 || c->sell_mode >= 5) && !c->h_verts.empty())
-                xyz = simplex_dof_coords(c->dim, c->p, c->ne, c->nd, c->nl, c->h_verts, c->h_dofs);
-            FaPattern P = fa_build_pattern(c->h_dofs, c->ne, c->nd, c->nl,
-                                           multi_rank(c) ? 0 : c->sell_mode, c->dim,
-                                           xyz.empty() ? nullptr : xyz.data(), c->sell_window, c->spmv_lds,
-                                           c->spmv_lpr);
-            if (P.lds_rows > 0) {
-                // the LDS-staged SpMV launches one block per window (rounded up to whole XCD ranges)
-                // and its CG form writes one partial per block: the grid must fit the partial slots
-                // (ADVICE r03).  Windows halve below their nominal size when halos are large, so the
-                // automatic choice falls back to the layout without LDS; an explicit one is refused.
-                const int64_t spw = P.lds_rows / (kLanes / std::max(1, P.lpr));
-                const int64_t nwin = ((int64_t)P.sptr.size() - 1 + spw - 1) / spw;
-                if (8 * ((nwin + 7) / 8) > kSpmvMaxBlocks) {
-                    if (c->spmv_lds >= 0)
-                        throw UnsupportedError("spmv_lds " + std::to_string(c->spmv_lds) + ": " +
-                                               std::to_string(nwin) + " LDS windows exceed the SpMV grid (" +
-                                               std::to_string(kSpmvMaxBlocks) + " blocks); use larger windows or 0");
-                    P = fa_build_pattern(c->h_dofs, c->ne, c->nd, c->nl, multi_rank(c) ? 0 : c->sell_mode,
-                                         c->dim, xyz.empty() ? nullptr : xyz.data(), c->sell_window, 0, 1);
-                }
-            }
-            const int64_t nslices = (int64_t)P.sptr.size() - 1;
-            if ((nslices + 3) / 4 + 8 > kSpmvMaxBlocks) throw UnsupportedError("matrix too large for the SpMV grid");
-            // built aside and moved into the context whole, after the last call that can throw
-            FaDeviceState F;
-            F.nnz = P.nnz;
-            upload(c, F.d_rowptr, P.rowptr);
-            upload(c, F.d_cols, P.cols);
-            upload(c, F.d_diagpos, P.diagpos);
-            upload(c, F.d_coff, P.coff);
-            upload(c, F.d_cpos, P.cpos);
-            F.d_vals.alloc(F.nnz);
-            F.d_vals_c.alloc(F.nnz);
-            F.d_Ee.alloc((size_t)c->nblk * c->nd * c->nd * kLanes);
-            F.nslices = nslices;
-            F.nstored = P.sptr.back();
-            upload(c, F.d_sptr, P.sptr);
-            upload(c, F.d_srows, P.srows);
-            upload(c, F.d_scols, P.scols);
-            upload(c, F.d_smap, P.smap);
-            F.d_svals.alloc(F.nstored);
-            F.d_svals_c.alloc(F.nstored);
-            F.sell_windowed = P.windowed;
-            if (!P.perm.empty()) {
-                upload(c, F.d_rperm, P.perm);
-                for (auto &v : F.d_pv) v.alloc(c->nl);
-            }
-            if (!P.sdel.empty()) upload(c, F.d_sdel, P.sdel);
-            if (P.lds_rows > 0) {  // LDS-staged windows (sell_plan.cpp)
-                upload(c, F.d_hptr, P.hptr);
-                upload(c, F.d_hidx, P.hidx);
-                upload(c, F.d_sloc, P.sloc);
-                F.lds_rows = P.lds_rows;
-                F.sell_lpr = P.lpr;
-                F.lds_max = P.lds_max;
-            }
-            if (!P.swide.empty()) {  // mixed layout: the slices beyond 16 bits stream d_scols
-                upload(c, F.d_swide, P.swide);
-                F.sell_nnz_wide = P.nnz_wide;
-            }
-            HIPCHK(hipStreamSynchronize(c->stream));  // P's host buffers die at scope exit
-            static_cast<FaDeviceState &>(*c) = std::move(F);
-            if (c->lds_rows > 0) c->lds_halo = (int64_t)P.hidx.size();
-        }
+        fa_ensure_pattern(c);
         // per-point coefficients at the rule of their integrator
         const size_t nqd = (size_t)c->ne * c->nq_sd, nqc = (size_t)c->ne * c->nq_scm;
         const DevBuf<double> dk = upload_opt(c, f->kappa_q, nqd), dkm = upload_opt(c, f->kappa_mat_q, nqd * c->dim * (c->dim + 1) / 2);
@@ -1126,38 +1140,12 @@ int cdfem_solve(cdfem_ctx *c, const cdfem_solver_params *p, const double *B, dou
         require_pa(c);
         require_partition(c);
         if (!p || !B || !X || !res) throw ArgError("null argument");
-        if (p->max_iter < 0) throw ArgError("max_iter < 0");
-        if (p->pc != CDFEM_PC_NONE && p->pc != CDFEM_PC_JACOBI && p->pc != CDFEM_PC_ILU)
-            throw ArgError("unknown preconditioner");
-        if (p->pc == CDFEM_PC_ILU && p->method == CDFEM_CG)
-            throw UnsupportedError("ILU(0) preconditions GMRES (a nonsymmetric preconditioner for CG)");
         *res = cdfem_solver_result{};
-        if (p->method != CDFEM_CG && p->method != CDFEM_GMRES && p->method != CDFEM_BICGSTAB)
-            throw ArgError("unknown method");
+        check_solver_params(*p);
         c->last_method = p->method;
         const double *dB = dev_in(c, B, where, c->d_w[6], c->nl);
         double *dX = where == CDFEM_DEVICE ? X : c->d_w[1];
-        // permuted SpMV layout (sell_plan.cpp): the Krylov iteration runs in the SpMV's order, B in
-        // and X out are permuted once per solve.  ILU(0) factors the matrix in mesh order (PETSc's
-        // natural ordering), so it keeps the mesh order and permutes around each apply instead.
-        const bool pspace = c->fa_ready && c->d_rperm && !multi_rank(c) && p->pc != CDFEM_PC_ILU;
-        struct SpaceGuard {
-            cdfem_ctx *c;
-            ~SpaceGuard() { c->perm_space = false; }
-        } guard{c};
-        const double *dBs = dB;
-        double *dXs = dX;
-        if (pspace) {
-            HIPCHK(launch_perm(c, true, dB, c->d_pv[0]));
-            dBs = c->d_pv[0];
-            dXs = c->d_pv[1];
-            c->perm_space = true;
-        }
-        solve(c, *p, dBs, dXs, *res);
-        if (pspace) {
-            c->perm_space = false;
-            HIPCHK(launch_perm(c, false, dXs, dX));
-        }
+        solve_mesh_order(c, *p, dB, dX, *res);
         dev_out(c, X, where, dX, c->nl);
         HIPCHK(hipStreamSynchronize(c->stream));
         return res->converged ? CDFEM_OK : CDFEM_ERR_NOT_CONVERGED;

@@ -21,6 +21,7 @@
 
 #include "../../include/cdfem.h"
 #include "ctx_state.hpp"
+#include "dispatch.hpp"
 #include "options.hpp"
 
 namespace cdfem {
@@ -49,6 +50,8 @@ int mfem_simplex_rule(int dim, int order, std::vector<double> &xi, std::vector<d
 int simplex_rule_for_order(int dim, int order, std::vector<double> &xi, std::vector<double> &w);
 int simplex_ndofs(int dim, int p);
 void simplex_basis(int dim, int p, const double *xi, double *phi, double *dphi);
+// the same with the P3 tables formed in long double (1 ulp): for forms that interpolate a state from nodal values
+void simplex_basis_x(int dim, int p, const double *xi, double *phi, double *dphi);
 extern const int kSimplexEdge[6][2];
 double p3_edge_t(int k);
 // element partition helpers (partition.cpp, host only)
@@ -493,6 +496,15 @@ void sell_build(FaPattern &P, int64_t nl, const SellPlan &pl);
 FaPattern fa_build_pattern(const std::vector<int32_t> &elem_dofs, int ne, int nd, int64_t nl, int sell_mode,
                            int dim = 0, const double *dof_xyz = nullptr, int64_t sell_window = 0,
                            int64_t lds_rows = 0, int lpr = 1);
+// f(DIM, P) as constants for the simplex spaces: tetrahedra of p = 1, 2, triangles of p = 1, 2, 3
+template <class F>
+hipError_t dispatch_simplex(const cdfem_ctx *c, F &&f)
+{
+    if (c->p < 1 || c->p > 3) return hipErrorInvalidValue;
+    return dispatch_value<31, 32, 21, 22, 23>(10 * c->dim + c->p, hipErrorInvalidValue, [&](auto DP) {
+        return f(std::integral_constant<int, DP() / 10>{}, std::integral_constant<int, DP() % 10>{});
+    });
+}
 hipError_t launch_simplex_elem(cdfem_ctx *c, const double *kq, const double *kmq, double kappa, double alpha,
                                const double *conv, const double *cq, const double *mq, double mass);
 hipError_t launch_fa_assemble(cdfem_ctx *c);
@@ -548,6 +560,33 @@ hipError_t ilu_apply(cdfem_ctx *c);
 // f64 compute-rate probes: mode 0 VALU v_fma_f64, 1 v_mfma_f64_16x16x4_f64; *flops per launch
 hipError_t launch_fp64_probe(cdfem_ctx *c, int mode, double *out, double *flops);
 
+// ---- the nonlinear heat form (nl_kernels.hip; the Newton driver and the entry points: newton.hip) ----
+// dofs of the facet opposite local vertex f in the element's local dof order (vertices, then edge nodes):
+// row (space, f) of the table, spaces in the order triangles P1, P2, P3, tetrahedra P1, P2
+constexpr int kFacetMaxDofs = 6;
+__host__ __device__ constexpr int facet_space(int dim, int p) { return dim == 2 ? p - 1 : 2 + p; }
+__host__ __device__ constexpr int facet_ndofs(int dim, int p) { return dim == 2 ? p + 1 : (p + 1) * (p + 2) / 2; }
+__host__ __device__ constexpr int facet_dof(int dim, int p, int f, int k)
+{
+    constexpr int8_t t[5][4][kFacetMaxDofs] = {
+        {{1, 2}, {0, 2}, {0, 1}},
+        {{1, 2, 5}, {0, 2, 4}, {0, 1, 3}},
+        {{1, 2, 7, 8}, {0, 2, 5, 6}, {0, 1, 3, 4}},
+        {{1, 2, 3}, {0, 2, 3}, {0, 1, 3}, {0, 1, 2}},
+        {{1, 2, 3, 7, 8, 9}, {0, 2, 3, 5, 6, 9}, {0, 1, 3, 4, 6, 8}, {0, 1, 2, 4, 5, 7}}};
+    return t[facet_space(dim, p)][f][k];
+}
+// Ye (element-major E-vector) = the residual's element vectors at u, with u_old from c->nl
+hipError_t launch_nl_residual(cdfem_ctx *c, const double *u, double *Ye);
+// d_Ee = the Jacobian's element matrices at u (k_simplex_elem's layout)
+hipError_t launch_nl_gradient(cdfem_ctx *c, const double *u);
+// R = ess ? 0 : R - g; negR (may be null) = -R
+hipError_t launch_nl_finish(cdfem_ctx *c, double *R, const double *g, double *negR);
+// facet E-vector from the point values gq, then b = its per-dof sums in ascending facet order
+hipError_t launch_bdr_lf(cdfem_ctx *c, const double *gq, double *b);
+// the assembled operator's pattern on the device, built once per mesh (capi.hip; cdfem_fa_setup, cdfem_nl_gradient)
+void fa_ensure_pattern(cdfem_ctx *c);
+
 // ---- the operator and the Krylov drivers (solve.hip), the cost model (model.hip) ----------------
 bool use_brick(const cdfem_ctx *c);       // the p <= 2 brick kernels run the structured Mult and CG
 bool use_hobrick_cg(const cdfem_ctx *c);  // the p = 3, 4 block CG runs
@@ -557,6 +596,11 @@ void op_apply_global(cdfem_ctx *c, const double *x, double *y, bool constrained)
 void ensure_dinv(cdfem_ctx *c);           // d_dinv (and the pa_uniform_diag table) formed once per operator
 // the Krylov driver p.method and the context select; dB, dX on the device, in the solve's order
 void solve(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, double *dX, cdfem_solver_result &res);
+// what cdfem_solve refuses in its parameters (ArgError / UnsupportedError)
+void check_solver_params(const cdfem_solver_params &p);
+// solve with dB, dX in the mesh's dof order: under a permuted SpMV layout the Krylov iteration runs in the
+// SpMV's order, B in and X out permuted once per solve
+void solve_mesh_order(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, double *dX, cdfem_solver_result &res);
 inline int nq_of(const cdfem_ctx *c, const Rule1D &r) { return c->dim == 3 ? r.q1 * r.q1 * r.q1 : r.q1 * r.q1; }
 void kernel_name(const cdfem_ctx *c, int k, char *buf, size_t n);
 double kernel_flops(const cdfem_ctx *c, int k);

@@ -36,6 +36,32 @@ struct FaDeviceState {
     DevBuf<double> d_svals, d_svals_c;
 };
 
+// The nonlinear heat form and its Newton solve (cdfem_nl_setup, cdfem_bdr_set; nl_kernels.hip, newton.hip):
+// coefficients, the tables of the order 2p + 2 rule, the boundary facets with their rule and gather lists,
+// the Newton vectors (device-resident for a whole solve) and the history of the last solve.
+struct NlState {
+    bool ready = false;
+    double dt = 0.0, a0 = 0.0, a1 = 0.0, m0 = 0.0, m1 = 0.0, u_ref = 0.0;
+    int nq = 0;                         // points of the order 2p + 2 rule
+    std::vector<double> h_sxi;          // its points (reference coordinates)
+    DevBuf<double> d_tab;               // phi [nq][nd], dphi [nq][nd][dim], w [nq]
+    DevBuf<int32_t> d_edofs;            // [ne][nd] element dofs, element-major
+    DevBuf<double> d_u, d_R, d_rhs, d_dx;  // Newton iterate, residual, -residual, update
+    DevBuf<double> d_uold, d_g;         // u of the last step; the Neumann load (zero when unset)
+    DevBuf<double> d_norm;              // [1] a norm's square on its way to the host
+    // boundary linear form (cdfem_bdr_set)
+    int nbf = 0, nqb = 0, nfd = 0;      // facets, points per facet, dofs per facet
+    std::vector<int32_t> h_face_elem, h_face_local;
+    std::vector<double> h_bxi;          // [dim + 1][nqb][dim] facet points in the element's reference coordinates
+    DevBuf<int32_t> d_face_elem, d_face_local;
+    DevBuf<double> d_btab;              // phi [dim + 1][nqb][nfd] of the facet's dofs, w [nqb]
+    DevBuf<int32_t> d_b_off, d_b_pos;   // per dof: its entries of the facet E-vector, ascending facet
+    DevBuf<double> d_bYe, d_bgq;        // facet E-vector [nbf][nfd]; point values [nbf][nqb]
+    // per-iteration history of the last Newton solve
+    std::vector<double> hist_res, hist_upd;
+    std::vector<int32_t> hist_lin;
+};
+
 // Everything cdfem_mesh_upload / cdfem_mesh_upload_simplex start from scratch.  (The mesh's sizes, rules and
 // host copies are assigned by every upload before mesh_ready and stay in ContextState.)
 struct MeshState : FaDeviceState {
@@ -111,6 +137,7 @@ struct MeshState : FaDeviceState {
     DevBuf<double> d_lfq;               // cdfem_lf_assemble: the point values (kept across calls)
     DevBuf<double> d_bcgs;              // BiCGStab vectors x, r, rh, p, v, t (6 * padded nl)
     DevBuf<double> d_bcgs_part;         // BiCGStab partials [3 * blocks]
+    NlState heat;                       // the nonlinear heat form (cdfem_nl_setup)
 };
 
 // The rank partition of the L-vector (cdfem_set_slab / cdfem_set_shared), reset by partition_free

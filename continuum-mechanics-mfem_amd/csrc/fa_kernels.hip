@@ -594,16 +594,6 @@ k_perm_scatter(const int32_t *__restrict__ perm, const double *__restrict__ yp, 
 }
 
 // ---- launchers ---------------------------------------------------------------------------------
-// f(DIM, P) as constants for the simplex spaces: tetrahedra of p = 1, 2, triangles of p = 1, 2, 3
-template <class F>
-static hipError_t dispatch_simplex(const cdfem_ctx *c, F &&f)
-{
-    if (c->p < 1 || c->p > 3) return hipErrorInvalidValue;
-    return dispatch_value<31, 32, 21, 22, 23>(10 * c->dim + c->p, hipErrorInvalidValue, [&](auto DP) {
-        return f(std::integral_constant<int, DP() / 10>{}, std::integral_constant<int, DP() % 10>{});
-    });
-}
-
 hipError_t launch_simplex_elem(cdfem_ctx *c, const double *kq, const double *kmq, double kappa, double alpha,
                                const double *conv, const double *cq, const double *mq, double mass)
 {

@@ -66,6 +66,15 @@ void upload(cdfem_ctx *c, Buf<T, Mem> &b, const std::vector<T> &v)
     upload(c, b, v.data(), v.size());
 }
 
+// ---- call-order checks and copies of the entry points (capi.hip) -----------------------------------
+void require_mesh(cdfem_ctx *c);       // StateError before a mesh upload
+void require_pa(cdfem_ctx *c);         // ... before an operator setup
+void require_partition(cdfem_ctx *c);  // several ranks: a declared partition
+// a device pointer holding n doubles of src (staged through staging when src is on the host)
+const double *dev_in(cdfem_ctx *c, const double *src, int where, double *staging, size_t n);
+// dst (host: synchronous; device: unless it is dsrc itself) <- n doubles at dsrc
+void dev_out(cdfem_ctx *c, double *dst, int where, const double *dsrc, size_t n);
+
 // ---- profiling (capi.hip) -------------------------------------------------------------------------
 void prof_mark(cdfem_ctx *c, int k, bool begin);
 void prof_collect(cdfem_ctx *c);

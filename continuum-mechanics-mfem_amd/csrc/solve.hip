@@ -648,4 +648,38 @@ void solve(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, double 
     }
 }
 
+void check_solver_params(const cdfem_solver_params &p)
+{
+    if (p.max_iter < 0) throw ArgError("max_iter < 0");
+    if (p.pc != CDFEM_PC_NONE && p.pc != CDFEM_PC_JACOBI && p.pc != CDFEM_PC_ILU) throw ArgError("unknown preconditioner");
+    if (p.pc == CDFEM_PC_ILU && p.method == CDFEM_CG)
+        throw UnsupportedError("ILU(0) preconditions GMRES (a nonsymmetric preconditioner for CG)");
+    if (p.method != CDFEM_CG && p.method != CDFEM_GMRES && p.method != CDFEM_BICGSTAB) throw ArgError("unknown method");
+}
+
+void solve_mesh_order(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, double *dX, cdfem_solver_result &res)
+{
+    // permuted SpMV layout (sell_plan.cpp): the Krylov iteration runs in the SpMV's order, B in
+    // and X out are permuted once per solve.  ILU(0) factors the matrix in mesh order (PETSc's
+    // natural ordering), so it keeps the mesh order and permutes around each apply instead.
+    const bool pspace = c->fa_ready && c->d_rperm && !multi_rank(c) && p.pc != CDFEM_PC_ILU;
+    struct SpaceGuard {
+        cdfem_ctx *c;
+        ~SpaceGuard() { c->perm_space = false; }
+    } guard{c};
+    const double *dBs = dB;
+    double *dXs = dX;
+    if (pspace) {
+        HIPCHK(launch_perm(c, true, dB, c->d_pv[0]));
+        dBs = c->d_pv[0];
+        dXs = c->d_pv[1];
+        c->perm_space = true;
+    }
+    solve(c, p, dBs, dXs, res);
+    if (pspace) {
+        c->perm_space = false;
+        HIPCHK(launch_perm(c, false, dXs, dX));
+    }
+}
+
 }  // namespace cdfem

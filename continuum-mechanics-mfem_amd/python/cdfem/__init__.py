@@ -31,6 +31,7 @@ METHODS = {"cg": CG, "gmres": GMRES, "bicgstab": BICGSTAB, "bcgs": BICGSTAB}
 PC_NONE, PC_JACOBI, PC_ILU = 0, 1, 2
 _PCS = {"none": PC_NONE, "jacobi": PC_JACOBI, "ilu": PC_ILU}
 RULE_OPERATOR, RULE_LINEARFORM, RULE_ERROR, RULE_DIFFUSION, RULE_CONVECTION, RULE_MASS = 0, 1, 2, 3, 4, 5
+RULE_NONLINEAR = 6
 K_APPLY, K_E2L, K_UPDATE, K_DIRECTION, K_ORTH = 0, 1, 2, 3, 4
 
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_NOT_CONVERGED, ERR_COMM = range(7)
@@ -65,6 +66,23 @@ class FormCoeffs(C.Structure):
     _fields_ = [("kinds", C.c_uint), ("kappa", C.c_double), ("kappa_q", C.POINTER(C.c_double)),
                 ("kappa_mat_q", C.POINTER(C.c_double)), ("alpha", C.c_double), ("conv", C.POINTER(C.c_double)),
                 ("conv_q", C.POINTER(C.c_double)), ("mass", C.c_double), ("mass_q", C.POINTER(C.c_double))]
+
+
+class NlHeatCoeffs(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("dt", "a0", "a1", "m0", "m1", "u_ref")]
+
+
+class NewtonParams(C.Structure):
+    _fields_ = [("abs_tol", C.c_double), ("rel_tol", C.c_double), ("max_iter", C.c_int),
+                ("jacobian_rebuild_freq", C.c_int), ("print_level", C.c_int)]
+
+
+class NewtonResult(C.Structure):
+    _fields_ = [("converged", C.c_int), ("iterations", C.c_int), ("initial_residual", C.c_double),
+                ("final_residual", C.c_double), ("final_relative_residual", C.c_double),
+                ("initial_update_norm", C.c_double), ("final_update_norm", C.c_double),
+                ("linear_iterations", C.c_int), ("residual_seconds", C.c_double), ("jacobian_seconds", C.c_double),
+                ("linear_seconds", C.c_double)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p)
@@ -144,6 +162,18 @@ def _declare(L):
         "cdfem_kuhn_mesh": (C.c_int, [C.c_int] * 3 + [C.c_double, _dp, _ip, _ip, _dp]),
         "cdfem_gmsh_sizes": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]),
         "cdfem_gmsh_mesh": (C.c_int, [C.c_char_p, C.c_int, _dp, _ip, _ip, _dp]),
+        "cdfem_nl_setup": (C.c_int, [vp, C.POINTER(NlHeatCoeffs)]),
+        "cdfem_nl_set_old": (C.c_int, [vp, vp, C.c_int]),
+        "cdfem_nl_set_rhs": (C.c_int, [vp, vp, C.c_int]),
+        "cdfem_nl_residual": (C.c_int, [vp, vp, vp, C.c_int]),
+        "cdfem_nl_gradient": (C.c_int, [vp, vp, C.c_int]),
+        "cdfem_newton_solve": (C.c_int, [vp, C.POINTER(NewtonParams), C.POINTER(SolverParams), vp, C.c_int,
+                                         C.POINTER(NewtonResult)]),
+        "cdfem_newton_history": (C.c_int, [vp, _dp, _dp, _ip, C.c_int, C.POINTER(C.c_int)]),
+        "cdfem_bdr_set": (C.c_int, [vp, C.c_int, _ip, _ip]),
+        "cdfem_bdr_rule_size": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "cdfem_bdr_quadrature_points": (C.c_int, [vp, _dp, C.c_int]),
+        "cdfem_bdr_lf_assemble": (C.c_int, [vp, vp, vp, C.c_int]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -354,6 +384,28 @@ def gmsh_mesh(path, order, ess_attrs=None) -> Mesh:
     m = Mesh(d, order, verts, dofmap, nl.value, np.nonzero(sel)[0].astype(np.int32), xyz, simplex=True)
     m.bdr_mask = mask
     return m
+
+
+def boundary_facets(mesh: Mesh, select=None):
+    """The boundary facets of a simplex mesh as (elem, local_face) int32 arrays, local_face f = the facet
+    opposite local vertex f: the facets that belong to exactly one element, in ascending (element, f) order.
+    select: a predicate on the facet's vertex coordinates, an array (dim, dim), that keeps a facet when true
+    (the reference's BuildXYBoundaryMarkers picks the x-extremes this way,
+    nonlinear_convection_diffusion_1D.cpp:261).  Vertices are matched by their coordinates, bitwise."""
+    verts = np.asarray(mesh.verts, dtype=np.float64)
+    ne, nv, dim = verts.shape
+    if not mesh.simplex or nv != dim + 1:
+        raise ValueError("boundary_facets needs a simplex mesh")
+    _, vid = np.unique(verts.reshape(-1, dim), axis=0, return_inverse=True)
+    vid = np.asarray(vid).reshape(ne, nv)
+    keys = np.stack([np.sort(np.delete(vid, f, axis=1), axis=1) for f in range(nv)], axis=1)  # (ne, nv, dim)
+    _, inv, cnt = np.unique(keys.reshape(-1, dim), axis=0, return_inverse=True, return_counts=True)
+    once = (cnt[np.asarray(inv).reshape(-1)] == 1).reshape(ne, nv)
+    elem, face = np.nonzero(once)
+    if select is not None:
+        keep = np.array([bool(select(np.delete(verts[e], f, axis=0))) for e, f in zip(elem, face)], dtype=bool)
+        elem, face = elem[keep], face[keep]
+    return elem.astype(np.int32), face.astype(np.int32)
 
 
 def partition_rcb(mesh: Mesh, nranks) -> np.ndarray:
@@ -567,6 +619,116 @@ class Context:
         self._chk(rc, allow=() if raise_on_fail else (ERR_NOT_CONVERGED,))
         return X, dict(converged=bool(res.converged), iterations=res.iterations,
                        final_norm=res.final_norm, initial_norm=res.initial_norm, seconds=res.seconds)
+
+    # -- nonlinear heat form, Newton, boundary linear form (simplex meshes) --------------------------
+    def nl_setup(self, dt, a0, a1, m0, m1, u_ref=0.0):
+        """Backward-Euler quasi-linear heat form: a(u) = a0 + a1 (u - u_ref), m(u) = m0 + m1 (u - u_ref)."""
+        k = NlHeatCoeffs(float(dt), float(a0), float(a1), float(m0), float(m1), float(u_ref))
+        self._chk(self.L.cdfem_nl_setup(self.h, C.byref(k)))
+        return self
+
+    def nl_set_old(self, u_old, where=HOST):
+        """u_old of the form: a host array, or (where=DEVICE) a device pointer, e.g. the last step's solution."""
+        if where == HOST:
+            u_old = _f64(u_old)
+            self._chk(self.L.cdfem_nl_set_old(self.h, u_old.ctypes.data, HOST))
+        else:
+            self._chk(self.L.cdfem_nl_set_old(self.h, C.c_void_p(u_old), DEVICE))
+
+    def nl_set_rhs(self, g):
+        """The Neumann load subtracted from the residual (an L-vector; None: zero)."""
+        g = None if g is None else _f64(g)
+        self._chk(self.L.cdfem_nl_set_rhs(self.h, None if g is None else g.ctypes.data, HOST))
+
+    def nl_residual(self, u):
+        u = _f64(u)
+        R = np.zeros(self.nl)
+        self._chk(self.L.cdfem_nl_residual(self.h, u.ctypes.data, R.ctypes.data, HOST))
+        return R
+
+    def nl_gradient(self, u):
+        """Assemble J(u): afterwards mult, diagonal, fa_csr and solve act on it."""
+        u = _f64(u)
+        self._chk(self.L.cdfem_nl_gradient(self.h, u.ctypes.data, HOST))
+        return self
+
+    def _newton_args(self, abs_tol, rel_tol, max_iter, jacobian_rebuild_freq, method, pc, lin_rel_tol, lin_abs_tol,
+                     lin_max_iter, restart, check_every):
+        prm = NewtonParams(float(abs_tol), float(rel_tol), int(max_iter), int(jacobian_rebuild_freq), 0)
+        lin = SolverParams(method_id(method), _PCS[pc], int(lin_max_iter), int(restart), float(lin_rel_tol),
+                           float(lin_abs_tol), int(check_every), 0)
+        return prm, lin
+
+    def _newton_out(self, rc, res):
+        n = C.c_int()
+        self._chk(self.L.cdfem_newton_history(self.h, None, None, None, 0, C.byref(n)))
+        hr, hu, hl = np.zeros(n.value), np.zeros(n.value), np.zeros(n.value, dtype=np.int32)
+        self._chk(self.L.cdfem_newton_history(self.h, _p(hr), _p(hu), hl.ctypes.data_as(_ip), n.value, C.byref(n)))
+        info = {k: getattr(res, k) for k, _ in NewtonResult._fields_}
+        info["converged"] = bool(res.converged)
+        info["status"] = rc
+        return info, dict(residual=hr, update=hu, linear_iterations=hl)
+
+    def newton_solve(self, u0, abs_tol=1e-10, rel_tol=1e-8, max_iter=20, jacobian_rebuild_freq=1, method="gmres",
+                     pc="ilu", lin_rel_tol=1e-10, lin_abs_tol=1e-12, lin_max_iter=2000, restart=30, check_every=16,
+                     raise_on_fail=False):
+        """Newton on the nonlinear heat form from the initial guess u0 (newton_petsc_solver.hpp:180-259; the
+        linear defaults are Input/petsc_nonlinear.opts').  Returns (u, result, history): the result's fields
+        are cdfem_newton_result's plus status (the return code), the history holds the residual norm, update
+        norm and linear iterations of every Newton iteration."""
+        prm, lin = self._newton_args(abs_tol, rel_tol, max_iter, jacobian_rebuild_freq, method, pc, lin_rel_tol,
+                                     lin_abs_tol, lin_max_iter, restart, check_every)
+        res = NewtonResult()
+        u = _f64(u0).copy()
+        rc = self.L.cdfem_newton_solve(self.h, C.byref(prm), C.byref(lin), u.ctypes.data, HOST, C.byref(res))
+        msg = self.L.cdfem_last_error(self.h).decode()
+        self._chk(rc, allow=() if raise_on_fail else (ERR_NOT_CONVERGED,))
+        info, hist = self._newton_out(rc, res)
+        info["message"] = msg
+        return u, info, hist
+
+    def newton_solve_device(self, du, **kw):
+        """The same with u in device memory (pointer du, updated in place): returns (result, history)."""
+        keys = ("abs_tol", "rel_tol", "max_iter", "jacobian_rebuild_freq", "method", "pc", "lin_rel_tol",
+                "lin_abs_tol", "lin_max_iter", "restart", "check_every")
+        dflt = (1e-10, 1e-8, 20, 1, "gmres", "ilu", 1e-10, 1e-12, 2000, 30, 16)
+        prm, lin = self._newton_args(*[kw.get(k, d) for k, d in zip(keys, dflt)])
+        res = NewtonResult()
+        rc = self.L.cdfem_newton_solve(self.h, C.byref(prm), C.byref(lin), C.c_void_p(du), DEVICE, C.byref(res))
+        msg = self.L.cdfem_last_error(self.h).decode()
+        self._chk(rc, allow=(ERR_NOT_CONVERGED,))
+        info, hist = self._newton_out(rc, res)
+        info["message"] = msg
+        return info, hist
+
+    def bdr_set(self, elem, local_face):
+        """The boundary facets of the boundary linear form (boundary_facets(mesh, select))."""
+        e, f = _i32(elem), _i32(local_face)
+        if len(e) != len(f):
+            raise ValueError("elem and local_face differ in length")
+        self._chk(self.L.cdfem_bdr_set(self.h, len(e), e.ctypes.data_as(_ip), f.ctypes.data_as(_ip)))
+        self.nbf = len(e)
+        return self
+
+    def bdr_rule_size(self):
+        n = C.c_int()
+        self._chk(self.L.cdfem_bdr_rule_size(self.h, C.byref(n)))
+        return n.value
+
+    def bdr_quadrature_points(self):
+        """(nbf, nq, dim) physical coordinates of the boundary rule's points."""
+        xyz = np.zeros((self.nbf, self.bdr_rule_size(), self.mesh.dim))
+        self._chk(self.L.cdfem_bdr_quadrature_points(self.h, _p(xyz), HOST))
+        return xyz
+
+    def bdr_lf_assemble(self, g_q):
+        """b_i = int_boundary g phi_i from the values of g at bdr_quadrature_points()."""
+        g_q = _f64(g_q)
+        if g_q.size != self.nbf * self.bdr_rule_size():
+            raise ValueError("g_q must hold one value per boundary quadrature point")
+        b = np.zeros(self.nl)
+        self._chk(self.L.cdfem_bdr_lf_assemble(self.h, g_q.ctypes.data, b.ctypes.data, HOST))
+        return b
 
     # -- multi-GPU (z-slab element partition) ----------------------------------------------------
     def comm_init_rccl(self, rank, nranks, uid: bytes):

@@ -56,7 +56,8 @@ enum { CDFEM_PC_NONE = 0, CDFEM_PC_JACOBI = 1, CDFEM_PC_ILU = 2 };
  * name it too).  Simplices: each integrator its own rule, MFEM's GetRule on affine simplices on
  * MFEM's tabulated rules: DIFFUSION order 2p - 2, CONVECTION and MASS order 2p (OPERATOR refused). */
 enum { CDFEM_RULE_OPERATOR = 0, CDFEM_RULE_LINEARFORM = 1, CDFEM_RULE_ERROR = 2, CDFEM_RULE_DIFFUSION = 3,
-       CDFEM_RULE_CONVECTION = 4, CDFEM_RULE_MASS = 5 };
+       CDFEM_RULE_CONVECTION = 4, CDFEM_RULE_MASS = 5,
+       CDFEM_RULE_NONLINEAR = 6 /* simplices, after cdfem_nl_setup: the nonlinear heat form's rule, order 2p + 2 */ };
 /* kernel ids for cdfem_profile_read */
 enum { CDFEM_K_APPLY = 0, CDFEM_K_E2L = 1, CDFEM_K_UPDATE = 2, CDFEM_K_DIRECTION = 3, CDFEM_K_ORTH = 4,
        CDFEM_K_COUNT = 8 };
@@ -226,6 +227,75 @@ typedef struct {
 
 int cdfem_solve(cdfem_ctx *ctx, const cdfem_solver_params *prm, const double *B, double *X,
                 int where, cdfem_solver_result *res);
+
+/* ---- nonlinear heat form and Newton solve (simplex meshes, one rank) ------------------------------
+ * replaces: the ParNonlinearForm of nonlinear_convection_diffusion_1D.cpp with its NonlinearMassBEIntegrator
+ * (:418-507) and NonlinearDiffusionIntegrator (:509-642), Input/input_nonlinear_1d.yaml's coefficients:
+ * backward Euler for m(u) du/dt = div(a(u) grad u), a(u) = a0 + a1 (u - u_ref), m(u) = m0 + m1 (u - u_ref).
+ * With u_old an L-vector on the same space, W = w_q det J and the one rule both integrators use,
+ * IntRules.Get(geom, 2p + OrderW + 2) = MFEM's tabulated rule of order 2p + 2 on affine simplices
+ * (CDFEM_RULE_NONLINEAR):
+ *   R_i  = sum_q W [ m(u) (u - u_old) / dt phi_i + a(u) grad u . grad phi_i ] - g_i
+ *   J_ij = sum_q W [ (m(u) + m1 (u - u_old)) / dt phi_i phi_j + a(u) grad phi_i . grad phi_j
+ *                    + a1 phi_j (grad phi_i . grad u) ]
+ * Essential dofs follow MFEM's NonlinearForm: R is zero on essential rows, J has essential rows and columns
+ * eliminated with a unit diagonal, a Newton solve keeps the essential values of its initial guess.
+ * cdfem_nl_setup: the coefficients, the rule tables, u_old = 0 and g = 0 (CDFEM_ERR_UNSUPPORTED on a quad / hex
+ * mesh and on more than one rank).  The other calls return CDFEM_ERR_STATE before it.
+ * cdfem_nl_set_old: u_old = the last step's solution (GridFunctionCoefficient u_old_coeff, :817-820).
+ * cdfem_nl_set_rhs: g, the Neumann load subtracted from the residual (ShiftedResidualOperator::SetBoundaryRHS,
+ * :644-669, :836); NULL sets it to zero.
+ * cdfem_nl_residual: R(u) (ShiftedResidualOperator::Mult, :653-660).
+ * cdfem_nl_gradient: assembles J(u) on the GPU (ParNonlinearForm::GetGradient, :662-665) into the full
+ * assembly's CSR: afterwards cdfem_pa_mult, cdfem_pa_diagonal, cdfem_fa_csr and cdfem_solve act on J(u), the
+ * constrained forms on the eliminated matrix.                                                          */
+typedef struct { double dt, a0, a1, m0, m1, u_ref; } cdfem_nl_heat_coeffs;
+int cdfem_nl_setup(cdfem_ctx *ctx, const cdfem_nl_heat_coeffs *coeffs);
+int cdfem_nl_set_old(cdfem_ctx *ctx, const double *u_old, int where);
+int cdfem_nl_set_rhs(cdfem_ctx *ctx, const double *g, int where);
+int cdfem_nl_residual(cdfem_ctx *ctx, const double *u, double *R, int where);
+int cdfem_nl_gradient(cdfem_ctx *ctx, const double *u, int where);
+
+/* replaces: NewtonPetscSolver::Solve (newton_petsc_solver.hpp:180-259; Input/petsc_nonlinear.opts for the
+ * linear solve).  For iter = 0 .. max_iter - 1: R = residual(u), rn = ||R||_2; r0 = max(1, rn) on iteration 0;
+ * converged when rn < abs_tol or rn / r0 < rel_tol (iterations = iter, the updates taken); else J(u) is
+ * assembled when iter % jacobian_rebuild_freq == 0 (values < 1 count as 1), J dx = -R is solved from a zero
+ * guess with `linear` (cdfem_solve's parameters and semantics), and u += dx.  A linear solve that does not
+ * converge ends the Newton solve with CDFEM_ERR_NOT_CONVERGED and cdfem_last_error names the Newton iteration
+ * (the reference throws, :354-362).  Leaving the loop without convergence gives iterations = max_iter,
+ * converged = 0 and CDFEM_ERR_NOT_CONVERGED with the result filled.  A params field <= 0 takes the reference's
+ * default: abs_tol 1e-10, rel_tol 1e-8, max_iter 20, jacobian_rebuild_freq 1.  u: the initial guess on input,
+ * the solution on output.  u, R, dx and u_old stay on the device for the whole solve; per iteration the two
+ * norms and the linear solver's own polls reach the host.  initial_residual = r0, initial_update_norm =
+ * du0 = max(1, ||dx_0||); the *_seconds are host clocks around device-synchronised sections.
+ * cdfem_newton_history: residual norm, update norm and linear iterations of every iteration of the last
+ * Newton solve, the converged check included (update norm 0, linear iterations 0): the first min(cap, count)
+ * entries, the count into *count (arrays may be NULL).                                                  */
+typedef struct { double abs_tol, rel_tol; int max_iter, jacobian_rebuild_freq, print_level; } cdfem_newton_params;
+typedef struct {
+    int converged, iterations;
+    double initial_residual, final_residual, final_relative_residual, initial_update_norm, final_update_norm;
+    int linear_iterations;   /* summed over the Newton iterations */
+    double residual_seconds, jacobian_seconds, linear_seconds;
+} cdfem_newton_result;
+int cdfem_newton_solve(cdfem_ctx *ctx, const cdfem_newton_params *prm, const cdfem_solver_params *linear,
+                       double *u, int where, cdfem_newton_result *res);
+int cdfem_newton_history(cdfem_ctx *ctx, double *res, double *upd, int32_t *lin_its, int cap, int *count);
+
+/* ---- boundary linear form (simplex meshes) --------------------------------------------------------
+ * replaces: neumann_form.AddBoundaryIntegrator(new BoundaryLFIntegrator(flux_coeff), x_bdr); Assemble()
+ * (nonlinear_convection_diffusion_1D.cpp:830-831, :952-954).  cdfem_bdr_set: the nbf boundary facets as (element,
+ * local facet f = the facet opposite local vertex f); the facet's vertices are the element's other vertices in
+ * ascending local order and its dofs come from a table over the element's local dof order, so no facet dof
+ * list crosses the ABI.  The rule is BoundaryLFIntegrator's default (a = 1, b = 1: order p + 1 on the facet):
+ * segments Gauss-Legendre with (p + 1) / 2 + 1 points, triangular facets MFEM's tabulated rule of order p + 1.
+ * cdfem_bdr_quadrature_points: nbf * nq * dim physical coordinates, facet-major.
+ * cdfem_bdr_lf_assemble: b_i = sum_q w_q (edge length | |t1 x t2|) g_q phi_i(q), g_q the nbf * nq point
+ * values; b is an L-vector (what cdfem_nl_set_rhs takes).                                              */
+int cdfem_bdr_set(cdfem_ctx *ctx, int nbf, const int32_t *face_elem, const int32_t *face_local);
+int cdfem_bdr_rule_size(cdfem_ctx *ctx, int *nq_per_facet);
+int cdfem_bdr_quadrature_points(cdfem_ctx *ctx, double *xyz, int where);
+int cdfem_bdr_lf_assemble(cdfem_ctx *ctx, const double *g_q, double *b, int where);
 
 /* ---- HBM bandwidth probe: mode 0 read (16 B/lane), 1 read (8 B/lane), 2 copy (16 B/lane) of a
  * `bytes`-sized buffer, `reps` launches; returns achieved GB/s (bytes moved / time).
