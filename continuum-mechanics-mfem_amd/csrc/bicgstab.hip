@@ -41,51 +41,17 @@
 // iterations the host queued past the stop exit at entry and change nothing.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
-#include <type_traits>
 
-#include "brick_core.hpp"
-#include "cdfem_internal.hpp"
-#include "dispatch.hpp"
-#include "reduce.hpp"
+#include "krylov_core.hpp"
 
 namespace cdfem {
 
 // L-vector entries per thread of the vector kernels (EPT): 4, 5, 6 or 8, chosen per vector size by
-// bcgs_ept; a block covers kRedThreads * EPT entries
+// bcgs_ept; a block covers kRedThreads * EPT entries.  The row of A_c u (patch_row), the sums over the
+// partials and their all-reduce (summed, launch_summed) and the host poll (post_head): krylov_core.hpp
 static int bcgs_nb(int64_t n, int ept) { return (int)((n + (int64_t)kRedThreads * ept - 1) / ((int64_t)kRedThreads * ept)); }
 int bcgs_blocks(int64_t n) { return bcgs_nb(n, 4); }  // the most blocks any EPT launches (partials' size)
-
-// the head of the state into the pinned slot the host will read (post_poll of gmres.hip)
-__device__ inline void bcgs_post(const BcgsState *st, BcgsState *poll)
-{
-    if (!poll) return;
-    poll->done = st->done;
-    poll->converged = st->converged;
-    poll->its = st->its;
-    poll->breakdown = st->breakdown;
-    poll->dp = st->dp;
-    __threadfence_system();
-}
-
-// (A_c u)_k from the apply's output w (S == 0), or from the structured Mult's patch buffer: the row's
-// 1-8 patch entries in patch_sum8's order, the apply's input on the essential rows (S = 4p + 1)
-template <int S>
-__device__ __forceinline__ double bcgs_row(const double *__restrict__ w, const GmPatchSrc &ps, int64_t k)
-{
-    if constexpr (S == 0) {
-        return w[k];
-    } else {  // (n < 2^28 on the brick path: brick_fits)
-        const uint32_t gid = (uint32_t)k, plane = (uint32_t)(ps.g.Lx * ps.g.Ly);
-        const uint32_t gz = fdiv(gid, ps.fdxy), rem = gid - gz * plane, gy = fdiv(rem, ps.fdx);
-        const uint32_t gx = rem - gy * (uint32_t)ps.g.Lx;
-        const auto bp = brsrc(ps.pb, 8u * (uint32_t)ps.g.nbx * ps.g.nby * ps.g.nbz * (S * S * S));
-        double y = patch_sum8<S>(bp, ps.g, (int)gx, (int)gy, (int)gz);
-        if (ps.ess[k]) y = ps.x[k];  // A_c: the identity row
-        return y;
-    }
-}
 
 // ---- r = rh = M^{-1} b, partials of (r, r) ------------------------------------------------------
 template <int kBcEPT>
@@ -111,20 +77,14 @@ k_bcgs_init(const double *__restrict__ b, const double *__restrict__ dinv, doubl
 }
 
 // ---- dp = |r|, tolerance, the two stops before the first iteration, the first rho and beta -----
-// mode 0: one rank; mode 1: the local sum into red[] (all-reduced next); mode 2: the scalar logic
-// on the all-reduced sum, the same arithmetic on every rank
 __global__ void __launch_bounds__(1024)
 k_bcgs_start(const double *__restrict__ part, int nb, BcgsState *__restrict__ st, double rtol, double atol,
-             int max_it, int mode, BcgsState *__restrict__ poll)
+             int max_it, int mode, BcgsHead *__restrict__ poll)
 {
-    __shared__ double sh[1024 / 64];
-    const double sum = mode == 2 ? st->red[0] : sum_partials(part, nb, sh);
-    if (threadIdx.x != 0) return;
-    if (mode == 1) {
-        st->red[0] = sum;
-        return;
-    }
-    const double dp = sqrt(sum);
+    __shared__ double sh[1][1024 / 64];
+    double sums[1];
+    if (!summed(part, nb, st, mode, sh, sums)) return;
+    const double sum = sums[0], dp = sqrt(sum);
     st->dp = dp;
     st->res0 = dp;
     st->ttol = fmax(rtol * dp, atol);
@@ -147,7 +107,7 @@ k_bcgs_start(const double *__restrict__ part, int nb, BcgsState *__restrict__ st
         st->rho = sum;
         st->beta = sum;
     }
-    bcgs_post(st, poll);
+    post_head(st, poll);
 }
 
 // ---- p = r + beta (p - omega v) ------------------------------------------------------------------
@@ -190,7 +150,7 @@ k_bcgs_v(const double *__restrict__ w, const double *__restrict__ dinv, const do
     for (int e = 0; e < kBcEPT; ++e) {
         const int64_t k = base + (int64_t)e * kRedThreads;
         if (k < n) {
-            double y = bcgs_row<S>(w, ps, k);
+            double y = patch_row<S>(w, ps, k);
             if (dinv) y *= dinv[k];
             v[k] = y;
             if (k >= skip_lo) acc += y * rh[k];
@@ -203,14 +163,11 @@ k_bcgs_v(const double *__restrict__ w, const double *__restrict__ dinv, const do
 __global__ void __launch_bounds__(1024)
 k_bcgs_alpha(const double *__restrict__ part, int nb, BcgsState *__restrict__ st, int mode)
 {
-    __shared__ double sh[1024 / 64];
+    __shared__ double sh[1][1024 / 64];
     if (st->done) return;  // uniform: every thread reads the same flag before the reduction
-    const double d1 = mode == 2 ? st->red[0] : sum_partials(part, nb, sh);
-    if (threadIdx.x != 0) return;
-    if (mode == 1) {
-        st->red[0] = d1;
-        return;
-    }
+    double sums[1];
+    if (!summed(part, nb, st, mode, sh, sums)) return;
+    const double d1 = sums[0];
     if (d1 == 0.0) {
         st->breakdown = kBcgsBreakD1;
         st->done = 1;
@@ -257,7 +214,7 @@ k_bcgs_t(const double *__restrict__ w, const double *__restrict__ dinv, const do
     for (int e = 0; e < kBcEPT; ++e) {
         const int64_t k = base + (int64_t)e * kRedThreads;
         if (k < n) {
-            double y = bcgs_row<S>(w, ps, k);
+            double y = patch_row<S>(w, ps, k);
             if (dinv) y *= dinv[k];
             t[k] = y;
             if (k >= skip_lo) {
@@ -282,23 +239,9 @@ k_bcgs_omega(const double *__restrict__ part, int nb, BcgsState *__restrict__ st
 {
     __shared__ double sh[3][1024 / 64];
     if (st->done) return;
-    double d1, d2, ss;
-    if (mode == 2) {
-        d1 = st->red[0];
-        d2 = st->red[1];
-        ss = st->red[2];
-    } else {
-        d1 = sum_partials(part, nb, sh[0]);
-        d2 = sum_partials(part + nb, nb, sh[1]);
-        ss = sum_partials(part + 2 * (int64_t)nb, nb, sh[2]);
-    }
-    if (threadIdx.x != 0) return;
-    if (mode == 1) {
-        st->red[0] = d1;
-        st->red[1] = d2;
-        st->red[2] = ss;
-        return;
-    }
+    double sums[3];
+    if (!summed(part, nb, st, mode, sh, sums)) return;
+    const double d1 = sums[0], d2 = sums[1], ss = sums[2];
     if (d2 == 0.0) {  // t = 0: k_bcgs_x adds alpha p alone (omega 0), k_bcgs_rho ends the solve
         st->half = 1;
         st->ss = ss;
@@ -354,27 +297,16 @@ k_bcgs_x(double *__restrict__ x, const double *__restrict__ p, double *__restric
 // ---- dp = |r|, its, the stop tests; then the next iteration's rho = (r, rh) and beta --------------
 __global__ void __launch_bounds__(1024)
 k_bcgs_rho(const double *__restrict__ part, int nb, BcgsState *__restrict__ st, int mode,
-           BcgsState *__restrict__ poll)
+           BcgsHead *__restrict__ poll)
 {
     __shared__ double sh[2][1024 / 64];
     if (st->done) {
-        if (threadIdx.x == 0 && mode != 1) bcgs_post(st, poll);
+        if (threadIdx.x == 0) post_head(st, poll);
         return;
     }
-    double rr, rrh;
-    if (mode == 2) {
-        rr = st->red[0];
-        rrh = st->red[1];
-    } else {
-        rr = sum_partials(part, nb, sh[0]);
-        rrh = sum_partials(part + nb, nb, sh[1]);
-    }
-    if (threadIdx.x != 0) return;
-    if (mode == 1) {
-        st->red[0] = rr;
-        st->red[1] = rrh;
-        return;
-    }
+    double sums[2];
+    if (!summed(part, nb, st, mode, sh, sums)) return;
+    const double rr = sums[0], rrh = sums[1];
     st->its += 1;
     if (st->half) {  // d2 == 0
         st->dp = 0.0;
@@ -397,68 +329,41 @@ k_bcgs_rho(const double *__restrict__ part, int nb, BcgsState *__restrict__ st, 
             st->rho = rrh;
         }
     }
-    bcgs_post(st, poll);
+    post_head(st, poll);
 }
 
 // ---- launchers ---------------------------------------------------------------------------------
-// Entries per thread of the vector kernels: the smallest of 4, 5, 6, 8 whose grid is resident in one
-// round (blocks <= CUs x resident blocks per CU of the widest kernel, k_bcgs_x), so no tail of a few
-// blocks runs a second round alone (orth_ept of gmres.hip; C2: 2097 blocks against 2048 slots at EPT 4).
-// The choice is a function of the vector size alone, so a size's sums always run in the same order.
+// Entries per thread of the vector kernels (pick_ept): the smallest whose grid fits CUs x the resident
+// blocks of the widest kernel, k_bcgs_x, at that EPT
 static int bcgs_ept(cdfem_ctx *c)
 {
-    if (c->bcgs_ept_n == c->nl) return c->bcgs_ept_auto;
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    int ept = 8;
-    const auto fits = [&](auto E) {
-        int per = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_bcgs_x<E()>, kRedThreads, 0);
-        return (int64_t)bcgs_nb(c->nl, E()) <= (int64_t)std::max(cus, 1) * std::max(per, 1);
-    };
-    if (fits(std::integral_constant<int, 4>{})) ept = 4;
-    else if (fits(std::integral_constant<int, 5>{})) ept = 5;
-    else if (fits(std::integral_constant<int, 6>{})) ept = 6;
-    c->bcgs_ept_auto = ept;
-    c->bcgs_ept_n = c->nl;
-    return ept;
+    return cached_ept(c->bcgs_ept_auto, c->nl, [](int e) {
+        int64_t fit = 0;
+        with_ept(e, [&](auto E) { fit = resident_blocks(k_bcgs_x<E()>); });
+        return fit;
+    });
 }
 
-// f(EPT as a constant) for the context's choice
-template <class F>
-static void with_ept(cdfem_ctx *c, F &&f)
-{
-    if (!dispatch_value<5, 6, 8>(bcgs_ept(c), false, f)) f(std::integral_constant<int, 4>{});  // (any other: 4)
-}
-
-// multi-rank: partial sums -> local sums (mode 1) -> all-reduce over ranks -> scalar logic (mode 2);
-// every rank then runs the same scalar arithmetic on the same sums and takes the same branch
 hipError_t launch_bcgs_init(cdfem_ctx *c, const double *b, const double *dinv, double *r, double *rh, double *part,
-                            BcgsState *st, double rtol, double atol, int max_it, BcgsState *poll)
+                            BcgsState *st, double rtol, double atol, int max_it, BcgsHead *poll)
 {
-    const int nb = bcgs_nb(c->nl, bcgs_ept(c));
-    const bool mr = multi_rank(c);
-    with_ept(c, [&](auto E) {
+    const int ept = bcgs_ept(c), nb = bcgs_nb(c->nl, ept);
+    with_ept(ept, [&](auto E) {
         hipLaunchKernelGGL(k_bcgs_init<E()>, dim3(nb), dim3(kRedThreads), 0, c->stream, b, dinv, r, rh, (int64_t)c->nl,
                            (int64_t)c->skip_lo, part);
-        return true;
     });
-    hipLaunchKernelGGL(k_bcgs_start, dim3(1), dim3(1024), 0, c->stream, part, nb, st, rtol, atol, max_it, mr ? 1 : 0,
-                       mr ? nullptr : poll);
-    if (mr) {
-        comm_allreduce(c, st->red, 1);
-        hipLaunchKernelGGL(k_bcgs_start, dim3(1), dim3(1024), 0, c->stream, part, nb, st, rtol, atol, max_it, 2, poll);
-    }
+    launch_summed(c, st->red, 1, poll, [&](int mode, BcgsHead *slot) {
+        hipLaunchKernelGGL(k_bcgs_start, dim3(1), dim3(1024), 0, c->stream, part, nb, st, rtol, atol, max_it, mode,
+                           slot);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_bcgs_p(cdfem_ctx *c, const double *r, double *p, const double *v, BcgsState *st)
 {
-    with_ept(c, [&](auto E) {
+    with_ept(bcgs_ept(c), [&](auto E) {
         hipLaunchKernelGGL(k_bcgs_p<E()>, dim3(bcgs_nb(c->nl, E())), dim3(kRedThreads), 0, c->stream, r, p, v,
                            (int64_t)c->nl, st);
-        return true;
     });
     return hipGetLastError();
 }
@@ -467,63 +372,48 @@ hipError_t launch_bcgs_p(cdfem_ctx *c, const double *r, double *p, const double 
 hipError_t launch_bcgs_v(cdfem_ctx *c, const double *w, const double *dinv, const double *rh, double *v, double *r,
                          double *part, BcgsState *st, const GmPatchSrc *ps)
 {
-    if (ps && ps->S != 5 && ps->S != 9) return hipErrorInvalidValue;
-    const int nb = bcgs_nb(c->nl, bcgs_ept(c));
+    const int ept = bcgs_ept(c), nb = bcgs_nb(c->nl, ept);
     const int64_t n = c->nl;
-    const bool mr = multi_rank(c);
-    const GmPatchSrc src = ps ? *ps : GmPatchSrc{};
-    // (S: the side of the brick patch the result is read from, 0: w itself)
-    with_ept(c, [&](auto E) {
-        return dispatch_value<0, 5, 9>(ps ? ps->S : 0, false, [&](auto S) {
+    const hipError_t bad = with_patch_src(ps, [&](auto S, const GmPatchSrc &src) {
+        with_ept(ept, [&](auto E) {
             hipLaunchKernelGGL((k_bcgs_v<S(), E()>), dim3(nb), dim3(kRedThreads), 0, c->stream, w, dinv, rh, v, n,
                                (int64_t)c->skip_lo, part, st, src);
-            return true;
         });
     });
-    hipLaunchKernelGGL(k_bcgs_alpha, dim3(1), dim3(1024), 0, c->stream, part, nb, st, mr ? 1 : 0);
-    if (mr) {
-        comm_allreduce(c, st->red, 1);
-        hipLaunchKernelGGL(k_bcgs_alpha, dim3(1), dim3(1024), 0, c->stream, part, nb, st, 2);
-    }
-    with_ept(c, [&](auto E) {
+    if (bad != hipSuccess) return bad;
+    launch_summed<BcgsHead>(c, st->red, 1, nullptr, [&](int mode, BcgsHead *) {
+        hipLaunchKernelGGL(k_bcgs_alpha, dim3(1), dim3(1024), 0, c->stream, part, nb, st, mode);
+    });
+    with_ept(ept, [&](auto E) {
         hipLaunchKernelGGL(k_bcgs_s<E()>, dim3(nb), dim3(kRedThreads), 0, c->stream, r, v, n, st);
-        return true;
     });
     return hipGetLastError();
 }
 
 // t = M^{-1} A_c s from w (ps null) or the patch buffer, omega, the x and r update, the stop tests
 hipError_t launch_bcgs_t(cdfem_ctx *c, const double *w, const double *dinv, double *x, const double *p, double *r,
-                         double *t, const double *rh, double *part, BcgsState *st, BcgsState *poll,
+                         double *t, const double *rh, double *part, BcgsState *st, BcgsHead *poll,
                          const GmPatchSrc *ps)
 {
-    if (ps && ps->S != 5 && ps->S != 9) return hipErrorInvalidValue;
-    const int nb = bcgs_nb(c->nl, bcgs_ept(c));
+    const int ept = bcgs_ept(c), nb = bcgs_nb(c->nl, ept);
     const int64_t n = c->nl, lo = c->skip_lo;
-    const bool mr = multi_rank(c);
-    const GmPatchSrc src = ps ? *ps : GmPatchSrc{};
-    with_ept(c, [&](auto E) {
-        return dispatch_value<0, 5, 9>(ps ? ps->S : 0, false, [&](auto S) {
+    const hipError_t bad = with_patch_src(ps, [&](auto S, const GmPatchSrc &src) {
+        with_ept(ept, [&](auto E) {
             hipLaunchKernelGGL((k_bcgs_t<S(), E()>), dim3(nb), dim3(kRedThreads), 0, c->stream, w, dinv, r, t, n, lo,
                                part, nb, st, src);
-            return true;
         });
     });
-    hipLaunchKernelGGL(k_bcgs_omega, dim3(1), dim3(1024), 0, c->stream, part, nb, st, mr ? 1 : 0);
-    if (mr) {
-        comm_allreduce(c, st->red, 3);
-        hipLaunchKernelGGL(k_bcgs_omega, dim3(1), dim3(1024), 0, c->stream, part, nb, st, 2);
-    }
-    with_ept(c, [&](auto E) {
+    if (bad != hipSuccess) return bad;
+    launch_summed<BcgsHead>(c, st->red, 3, nullptr, [&](int mode, BcgsHead *) {
+        hipLaunchKernelGGL(k_bcgs_omega, dim3(1), dim3(1024), 0, c->stream, part, nb, st, mode);
+    });
+    with_ept(ept, [&](auto E) {
         hipLaunchKernelGGL(k_bcgs_x<E()>, dim3(nb), dim3(kRedThreads), 0, c->stream, x, p, r, t, rh, n, lo, part, nb,
                            st);
-        return true;
     });
-    hipLaunchKernelGGL(k_bcgs_rho, dim3(1), dim3(1024), 0, c->stream, part, nb, st, mr ? 1 : 0, mr ? nullptr : poll);
-    if (mr) {
-        comm_allreduce(c, st->red, 2);
-        hipLaunchKernelGGL(k_bcgs_rho, dim3(1), dim3(1024), 0, c->stream, part, nb, st, 2, poll);
-    }
+    launch_summed(c, st->red, 2, poll, [&](int mode, BcgsHead *slot) {
+        hipLaunchKernelGGL(k_bcgs_rho, dim3(1), dim3(1024), 0, c->stream, part, nb, st, mode, slot);
+    });
     return hipGetLastError();
 }
 

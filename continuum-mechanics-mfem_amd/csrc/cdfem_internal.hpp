@@ -15,6 +15,7 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -22,6 +23,7 @@
 #include "../../include/cdfem.h"
 #include "ctx_state.hpp"
 #include "dispatch.hpp"
+#include "krylov_host.hpp"
 #include "options.hpp"
 
 namespace cdfem {
@@ -82,13 +84,14 @@ struct KrylovState {
                     // the update logic, so no further apply folded it): k_cg_xflush applies it
 };
 
-// Device-side GMRES(m) state (gmres.hip).  The first 32 bytes are what the host polls.
+// Device-side GMRES(m) state (gmres.hip).  The host polls the head: the pinned slots hold heads (post_head)
 constexpr int kGmMaxRestart = 64;
-struct GmresState {
+struct GmresHead {
     int cycle_done, done, converged, its;
     double res;
     int j, kk;
-    // ----
+};
+struct GmresState : GmresHead {
     int max_it, m;
     double ttol, res0;
     double s[kGmMaxRestart + 1];   // basis scales: v_i = s_i * V_i
@@ -97,19 +100,24 @@ struct GmresState {
     double red[kGmMaxRestart + 1];  // multi-rank: rank-local sums awaiting the all-reduce
     double y[kGmMaxRestart];        // cycle end: the least-squares solution, scaled by s
 };
-constexpr size_t kGmPollBytes = 32;
 
-// Device-side BiCGStab state (bicgstab.hip).  The first 24 bytes are what the host polls.
+// Device-side BiCGStab state (bicgstab.hip), its head polled as GMRES's is.
 enum : int { kBcgsBreakRho = 1, kBcgsBreakD1 = 2, kBcgsBreakD2 = 3 };  // BcgsState::breakdown
 constexpr int kBcgsSlots = 4;  // pinned poll slots of the iterations, + 1 for the start
-struct BcgsState {
+struct BcgsHead {
     int done, converged, its, breakdown;
     double dp;
-    // ----
+};
+struct BcgsState : BcgsHead {
     int half, max_it;              // half: d2 == 0, the x update adds alpha p alone and the solve ends
     double ttol, res0, rho, alpha, omega, beta, ss;
     double red[4];                 // multi-rank: rank-local sums awaiting the all-reduce
 };
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"  // (a state with a base is not standard-layout: base first)
+static_assert(sizeof(GmresHead) == 32 && offsetof(GmresState, cycle_done) == 0 && offsetof(GmresState, max_it) == 32);
+static_assert(sizeof(BcgsHead) == 24 && offsetof(BcgsState, done) == 0 && offsetof(BcgsState, half) == 24);
+#pragma clang diagnostic pop
 
 // A captured graph and its executable, destroyed with their owner
 struct SweepGraph {
@@ -227,19 +235,15 @@ struct ContextState : Streams {
     DevBuf<KrylovState> d_state;
     PinBuf<KrylovState> h_state;
     DevBuf<GmresState> d_gmst;          // device GMRES state
-    PinBuf<GmresState> h_gmpoll;        // kGmMaxRestart + 1 poll slots
+    PinBuf<GmresHead> h_gmpoll;         // kGmMaxRestart + 1 poll slots
     Event gm_ev[2];
     DevBuf<BcgsState> d_bcst;           // device BiCGStab state
-    PinBuf<BcgsState> h_bcpoll;         // kBcgsSlots + 1 poll slots
+    PinBuf<BcgsHead> h_bcpoll;          // kBcgsSlots + 1 poll slots
     Event bc_ev[2];
     int last_method = -1;               // method of the last cdfem_solve (kernel_bytes / kernel_name of CDFEM_K_UPDATE)
     int bcgs_src = 0;                   // the last BiCGStab solve's operator source: 0 the Mult's output, else the patch side
     int bcgs_diag = 0;                  // the last BiCGStab solve read a Jacobi diagonal
-    // entries per thread of the GMRES / BiCGStab vector kernels, cached for vectors of *_ept_n entries
-    int gm_ept_auto = 4;
-    int64_t gm_ept_n = -1;
-    int bcgs_ept_auto = 4;
-    int64_t bcgs_ept_n = -1;
+    EptCache gm_ept_auto, bcgs_ept_auto;  // entries per thread of the GMRES / BiCGStab vector kernels (pick_ept)
 
     // profiling
     bool profile = false;
@@ -535,22 +539,22 @@ int gmres_blocks(int64_t n);
 hipError_t launch_gm_init(cdfem_ctx *c, GmresState *st, int m, int max_it);
 // poll: pinned host slot the step's last scalar kernel writes the state head into (solve_gmres)
 hipError_t launch_gm_residual(cdfem_ctx *c, const double *b, const double *Ax, const double *dinv, double *v0,
-                              double *part, GmresState *st, bool first, double rtol, double atol, GmresState *poll);
+                              double *part, GmresState *st, bool first, double rtol, double atol, GmresHead *poll);
 // ps (gm_pb): pass 1 reads the structured Mult's patch buffer for A_c V_j instead of w (brick_core.hpp)
 struct GmPatchSrc;
 hipError_t launch_gm_orth(cdfem_ctx *c, double *w, const double *dinv, double *V, int64_t ldv, double *part,
-                          GmresState *st, int m, GmresState *poll, const GmPatchSrc *ps = nullptr);
-hipError_t launch_gm_update(cdfem_ctx *c, double *x, const double *V, int64_t ldv, GmresState *st, GmresState *poll);
+                          GmresState *st, int m, GmresHead *poll, const GmPatchSrc *ps = nullptr);
+hipError_t launch_gm_update(cdfem_ctx *c, double *x, const double *V, int64_t ldv, GmresState *st, GmresHead *poll);
 
 // BiCGStab (bicgstab.hip); ps as for launch_gm_orth: k_bcgs_v / k_bcgs_t read the patch buffer instead of w
 int bcgs_blocks(int64_t n);
 hipError_t launch_bcgs_init(cdfem_ctx *c, const double *b, const double *dinv, double *r, double *rh, double *part,
-                            BcgsState *st, double rtol, double atol, int max_it, BcgsState *poll);
+                            BcgsState *st, double rtol, double atol, int max_it, BcgsHead *poll);
 hipError_t launch_bcgs_p(cdfem_ctx *c, const double *r, double *p, const double *v, BcgsState *st);
 hipError_t launch_bcgs_v(cdfem_ctx *c, const double *w, const double *dinv, const double *rh, double *v, double *r,
                          double *part, BcgsState *st, const GmPatchSrc *ps = nullptr);
 hipError_t launch_bcgs_t(cdfem_ctx *c, const double *w, const double *dinv, double *x, const double *p, double *r,
-                         double *t, const double *rh, double *part, BcgsState *st, BcgsState *poll,
+                         double *t, const double *rh, double *part, BcgsState *st, BcgsHead *poll,
                          const GmPatchSrc *ps = nullptr);
 hipError_t launch_stream(cdfem_ctx *c, int mode, const double *a, double *b, int64_t n);
 // ILU(0) (ilu_kernels.hip): factor + capture once per operator; apply: ilu.z = (LU)^{-1} d_w[4]

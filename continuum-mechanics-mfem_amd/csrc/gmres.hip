@@ -19,12 +19,7 @@
 // of a cycle exit at entry.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
-#include "brick_core.hpp"
-#include "cdfem_internal.hpp"
-#include "dispatch.hpp"
-#include "reduce.hpp"
+#include "krylov_core.hpp"
 
 namespace cdfem {
 
@@ -58,37 +53,16 @@ k_gm_residual(const double *__restrict__ b, const double *__restrict__ Ax, const
     store_partial(block_sum(acc, sh), part);
 }
 
-// host poll without a copy kernel: the last scalar kernel of every polled step writes the head of
-// the state (kGmPollBytes: cycle_done, done, converged, its, res, j, kk) straight into the
-// pinned host slot the host will wait on (hipHostMalloc memory is device-visible).  A D2H
-// hipMemcpyAsync of the same 32 bytes cost a 4 us blit kernel per GMRES step.
-__device__ inline void post_poll(const GmresState *st, GmresState *poll)
-{
-    if (!poll) return;
-    poll->cycle_done = st->cycle_done;
-    poll->done = st->done;
-    poll->converged = st->converged;
-    poll->its = st->its;
-    poll->res = st->res;
-    poll->j = st->j;
-    poll->kk = st->kk;
-    __threadfence_system();
-}
-
 // ---- start of a cycle: beta = |v0|, first-cycle tolerance, convergence / max_it test ------------
 __global__ void __launch_bounds__(1024)
 k_gm_start(const double *__restrict__ part, int nb, GmresState *__restrict__ st, int first, double rtol,
-           double atol, int mode, GmresState *__restrict__ poll)
+           double atol, int mode, GmresHead *__restrict__ poll)
 {
-    __shared__ double sh[1024 / 64];
-    const double sum = mode == 2 ? st->red[0] : sum_partials(part, nb, sh);
-    if (threadIdx.x != 0) return;
-    if (mode == 1) {  // multi-rank: local sum, all-reduced before the mode-2 launch
-        st->red[0] = sum;
-        return;
-    }
+    __shared__ double sh[1][1024 / 64];
+    double sum[1];
+    if (!summed(part, nb, st, mode, sh, sum)) return;
     if (!st->done) {
-        const double beta = sqrt(sum);
+        const double beta = sqrt(sum[0]);
         st->res = beta;
         if (first) {
             st->ttol = fmax(rtol * beta, atol);
@@ -109,7 +83,7 @@ k_gm_start(const double *__restrict__ part, int nb, GmresState *__restrict__ st,
             st->cycle_done = 0;
         }
     }
-    post_poll(st, poll);
+    post_head(st, poll);
 }
 
 // ---- pass 1: w = s_j M^{-1} A V_j (in place over the apply output), partial (w, V_i), i <= j ----
@@ -118,8 +92,8 @@ k_gm_start(const double *__restrict__ part, int nb, GmresState *__restrict__ st,
 // dropped).  Each wave parks its wave sums in LDS, so the whole step needs ONE barrier before the
 // block sums.  Measured at C4 (orthogonalisation per step): one barrier per batch of 8, 93.9 us;
 // one barrier in all, batches of 8 / 4 / 2 / 1: 85.7 / 83.2 / 82.6 / 82.1 us.
-// S > 0 (gm_pb, GmPatchSrc): A_c V_j from the structured Mult's patch buffer (patch_sum8, S = 4p + 1)
-// instead of w; w is still written (pass 2 reads it)
+// S > 0 (gm_pb, GmPatchSrc): A_c V_j from the structured Mult's patch buffer (patch_row) instead of w; w is
+// still written (pass 2 reads it)
 template <int BAT, int EPT, int S = 0>
 __global__ void __launch_bounds__(kRedThreads)
 k_gm_pass1(double *__restrict__ w, const double *__restrict__ dinv, const double *__restrict__ V, int64_t n,
@@ -138,18 +112,7 @@ k_gm_pass1(double *__restrict__ w, const double *__restrict__ dinv, const double
         const int64_t k = base + (int64_t)e * kRedThreads;
         double v = 0.0;
         if (k < n) {
-            double y;
-            if constexpr (S == 0) {
-                y = w[k];
-            } else {  // (n < 2^28 on the brick path: brick_fits)
-                const uint32_t gid = (uint32_t)k, plane = (uint32_t)(ps.g.Lx * ps.g.Ly);
-                const uint32_t gz = fdiv(gid, ps.fdxy), rem = gid - gz * plane, gy = fdiv(rem, ps.fdx);
-                const uint32_t gx = rem - gy * (uint32_t)ps.g.Lx;
-                const auto bp = brsrc(ps.pb, 8u * (uint32_t)ps.g.nbx * ps.g.nby * ps.g.nbz * (S * S * S));
-                y = patch_sum8<S>(bp, ps.g, (int)gx, (int)gy, (int)gz);
-                if (ps.ess[k]) y = ps.x[k];  // A_c: the identity row
-            }
-            v = sj * y;
+            v = sj * patch_row<S>(w, ps, k);
             if (dinv) v *= dinv[k];
             w[k] = v;
         }
@@ -190,40 +153,19 @@ k_gm_pass1(double *__restrict__ w, const double *__restrict__ dinv, const double
     }
 }
 
-// ---- H[i][j] = s_i * sum_b part[i][b], one wave per i (fixed order) ------------------------------
+// ---- several ranks: H[i][j] = s_i * red[i] from the all-reduced sums of k_gm_dots_fin_mb ---------
 __global__ void __launch_bounds__(1024)
-k_gm_dots_fin(const double *__restrict__ part, int nb, GmresState *__restrict__ st, int mode)
+k_gm_dots_fin(GmresState *__restrict__ st)
 {
     if (st->cycle_done) return;
     const int j = st->j;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (mode == 2) {  // multi-rank: H[i][j] from the all-reduced sums
-        if (threadIdx.x <= j) st->H[threadIdx.x * kGmMaxRestart + j] = st->s[threadIdx.x] * st->red[threadIdx.x];
-        return;
-    }
-    for (int i = wv; i <= st->m; i += 16) {
-        // 8 independent partial loads per lane in flight, combined in a fixed order
-        double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (i <= j) {
-            const double *pi = part + (int64_t)i * nb;
-            int b = lane;
-            for (; b + 7 * 64 < nb; b += 8 * 64) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) a[u] += pi[b + u * 64];
-            }
-            for (int u = 0; b < nb; b += 64, ++u) a[u] += pi[b];
-        }
-        double v = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-        v = wave_sum(v);
-        if (lane != 0) continue;
-        if (mode == 1) st->red[i] = v;  // multi-rank: local sums (zero past j), all-reduced next
-        else if (i <= j) st->H[i * kGmMaxRestart + j] = st->s[i] * v;
-    }
+    if (threadIdx.x <= j) st->H[threadIdx.x * kGmMaxRestart + j] = st->s[threadIdx.x] * st->red[threadIdx.x];
 }
 
-// ---- H[i][j] = s_i * sum_b part[i][b] (modes 0 / 1 of k_gm_dots_fin), one block per i ------------
+// ---- H[i][j] = s_i * sum_b part[i][b], one block per i --------------------------------------------
 // Every projection's partials are summed by a block of its own (fixed order), so the step's
-// projections reduce in parallel instead of 16 at a time in one block.
+// projections reduce in parallel.  mode 0: one rank, H[i][j] itself; mode 1: the local sums into red[]
+// (zero past j), all-reduced before k_gm_dots_fin forms H[i][j] from them.
 __global__ void __launch_bounds__(kRedThreads)
 k_gm_dots_fin_mb(const double *__restrict__ part, int nb, GmresState *__restrict__ st, int mode)
 {
@@ -307,13 +249,13 @@ k_gm_pass2(const double *__restrict__ w, double *__restrict__ V, int64_t n, int6
 // ---- h_{j+1,j}, Givens rotations, residual estimate, cycle control ------------------------------
 __global__ void __launch_bounds__(1024)
 k_gm_norm_fin(const double *__restrict__ part, int nb, GmresState *__restrict__ st, int mode,
-              GmresState *__restrict__ poll)
+              GmresHead *__restrict__ poll)
 {
     constexpr int LD = kGmMaxRestart;
-    __shared__ double sh[1024 / 64];
+    __shared__ double sh[1][1024 / 64];
     __shared__ double hc[kGmMaxRestart + 1], cs[kGmMaxRestart], sn[kGmMaxRestart];
     if (st->cycle_done) {  // uniform: every thread reads the same flag before the reduction
-        if (threadIdx.x == 0 && mode != 1) post_poll(st, poll);
+        if (threadIdx.x == 0) post_head(st, poll);
         return;
     }
     const int j = st->j;
@@ -324,14 +266,11 @@ k_gm_norm_fin(const double *__restrict__ part, int nb, GmresState *__restrict__ 
         cs[threadIdx.x] = st->cs[threadIdx.x];
         sn[threadIdx.x] = st->sn[threadIdx.x];
     }
-    const double sum = mode == 2 ? st->red[0] : sum_partials(part, nb, sh);  // (contains a barrier)
-    if (mode == 2) __syncthreads();
-    if (threadIdx.x != 0) return;
-    if (mode == 1) {  // multi-rank: local sum, all-reduced before the mode-2 launch
-        st->red[0] = sum;
-        return;
-    }
-    const double hn = sqrt(sum);
+    double sum[1];
+    const bool logic = summed(part, nb, st, mode, sh, sum);  // (modes 0 and 1: contains a barrier)
+    if (mode == 2) __syncthreads();                           // hc, cs, sn are published either way
+    if (!logic) return;
+    const double hn = sqrt(sum[0]);
     hc[j + 1] = hn;
     for (int i = 0; i < j; ++i) {
         const double a = hc[i], c2 = hc[i + 1];
@@ -355,7 +294,7 @@ k_gm_norm_fin(const double *__restrict__ part, int nb, GmresState *__restrict__ 
     st->s[j + 1] = (hn != 0.0) ? 1.0 / hn : 0.0;
     st->j = j + 1;
     if (hn == 0.0 || st->res <= st->ttol || j + 1 == st->m || st->its >= st->max_it) st->cycle_done = 1;
-    post_poll(st, poll);
+    post_head(st, poll);
 }
 
 // ---- end of cycle: y = H_k^{-1} g_k (every block, redundantly: k <= 64), x += sum_i y_i s_i V_i --
@@ -434,7 +373,7 @@ k_gm_update(double *__restrict__ x, const double *__restrict__ V, int64_t n, int
     }
 }
 
-__global__ void k_gm_cycle_end(GmresState *__restrict__ st, GmresState *__restrict__ poll)
+__global__ void k_gm_cycle_end(GmresState *__restrict__ st, GmresHead *__restrict__ poll)
 {
     if (!st->done) {
         if (st->res <= st->ttol) {
@@ -444,7 +383,7 @@ __global__ void k_gm_cycle_end(GmresState *__restrict__ st, GmresState *__restri
             st->done = 1;
         }
     }
-    post_poll(st, poll);
+    post_head(st, poll);
 }
 
 __global__ void k_gm_init(GmresState *__restrict__ st, int m, int max_it)
@@ -469,93 +408,58 @@ hipError_t launch_gm_init(cdfem_ctx *c, GmresState *st, int m, int max_it)
     return hipGetLastError();
 }
 
-// multi-rank: partial sums -> local sum (mode 1) -> all-reduce over ranks -> scalar logic (mode 2);
-// every rank then runs the same scalar arithmetic on the same sums and takes the same branches
-static int64_t owned_from(const cdfem_ctx *c) { return c->skip_lo; }
-static double *red_of(GmresState *st) { return st->red; }
-
 hipError_t launch_gm_residual(cdfem_ctx *c, const double *b, const double *Ax, const double *dinv, double *v0,
-                              double *part, GmresState *st, bool first, double rtol, double atol, GmresState *poll)
+                              double *part, GmresState *st, bool first, double rtol, double atol, GmresHead *poll)
 {
     const int nb = gmres_blocks(c->nl);
-    const bool mr = multi_rank(c);
     hipLaunchKernelGGL(k_gm_residual, dim3(nb), dim3(kRedThreads), 0, c->stream, b, Ax, dinv, v0,
-                       (int64_t)c->nl, owned_from(c), part, st);
-    hipLaunchKernelGGL(k_gm_start, dim3(1), dim3(1024), 0, c->stream, part, nb, st, first ? 1 : 0, rtol, atol,
-                       mr ? 1 : 0, mr ? nullptr : poll);
-    if (mr) {
-        comm_allreduce(c, red_of(st), 1);
-        hipLaunchKernelGGL(k_gm_start, dim3(1), dim3(1024), 0, c->stream, part, nb, st, first ? 1 : 0, rtol, atol, 2,
-                           poll);
-    }
+                       (int64_t)c->nl, (int64_t)c->skip_lo, part, st);
+    launch_summed(c, st->red, 1, poll, [&](int mode, GmresHead *slot) {
+        hipLaunchKernelGGL(k_gm_start, dim3(1), dim3(1024), 0, c->stream, part, nb, st, first ? 1 : 0, rtol, atol,
+                           mode, slot);
+    });
     return hipGetLastError();
 }
 
-// Entries per thread of the two orthogonalisation passes: the smallest of 4, 5, 6, 8 whose grid is
-// resident in one round (blocks <= CUs x resident blocks per CU), so no tail of a few blocks runs
-// a second round alone (C2: 2097 blocks of 1024 entries against 2048 resident slots at EPT 4).
+// Entries per thread of the two orthogonalisation passes (pick_ept): set_option("gm_ept"), else the smallest
+// whose grid fits CUs x the resident blocks of pass 1 at EPT 4
 static int orth_ept(cdfem_ctx *c)
 {
-    if (c->gm_ept) return c->gm_ept;                  // set_option("gm_ept")
-    if (c->gm_ept_n == c->nl) return c->gm_ept_auto;  // chosen for this size already
-    int dev = 0, cus = 0, per = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_gm_pass1<kGmBatch, 4, 0>, kRedThreads, 0);
-    const int64_t cap = (int64_t)std::max(cus, 1) * std::max(per, 1);
-    int ept = 8;
-    for (int e : {4, 5, 6, 8})
-        if ((c->nl + (int64_t)kRedThreads * e - 1) / ((int64_t)kRedThreads * e) <= cap) {
-            ept = e;
-            break;
-        }
-    c->gm_ept_auto = ept;
-    c->gm_ept_n = c->nl;
-    return ept;
-}
-
-template <int EPT>
-static void orth_passes(cdfem_ctx *c, double *w, const double *dinv, double *V, int64_t ldv, double *part,
-                        GmresState *st, int m, GmresState *poll, const GmPatchSrc *ps)
-{
-    const int nb = (int)((c->nl + (int64_t)kRedThreads * EPT - 1) / ((int64_t)kRedThreads * EPT));
-    const int64_t n = c->nl;
-    const bool mr = multi_rank(c);
-    const GmPatchSrc src = ps ? *ps : GmPatchSrc{};
-    // (S: the side of the brick patch w is read from, 0: w itself; launch_gm_orth admits 5 and 9)
-    (void)dispatch_value<0, 5, 9>(ps ? ps->S : 0, false, [&](auto S) {
-        hipLaunchKernelGGL((k_gm_pass1<kGmBatch, EPT, S()>), dim3(nb), dim3(kRedThreads), 0, c->stream, w, dinv, V, n,
-                           ldv, owned_from(c), part, nb, st, src);
-        return true;
-    });
-    hipLaunchKernelGGL(k_gm_dots_fin_mb, dim3(m + 1), dim3(kRedThreads), 0, c->stream, part, nb, st, mr ? 1 : 0);
-    if (mr) {
-        comm_allreduce(c, red_of(st), m + 1);
-        hipLaunchKernelGGL(k_gm_dots_fin, dim3(1), dim3(1024), 0, c->stream, part, nb, st, 2);
-    }
-    hipLaunchKernelGGL((k_gm_pass2<kGmBatch2, EPT>), dim3(nb), dim3(kRedThreads), 0, c->stream, w, V, n, ldv,
-                       owned_from(c), part, st);
-    hipLaunchKernelGGL(k_gm_norm_fin, dim3(1), dim3(1024), 0, c->stream, part, nb, st, mr ? 1 : 0,
-                       mr ? nullptr : poll);
-    if (mr) {
-        comm_allreduce(c, red_of(st), 1);
-        hipLaunchKernelGGL(k_gm_norm_fin, dim3(1), dim3(1024), 0, c->stream, part, nb, st, 2, poll);
-    }
+    if (c->gm_ept) return c->gm_ept;
+    return cached_ept(c->gm_ept_auto, c->nl, [](int) { return resident_blocks(k_gm_pass1<kGmBatch, 4, 0>); });
 }
 
 hipError_t launch_gm_orth(cdfem_ctx *c, double *w, const double *dinv, double *V, int64_t ldv, double *part,
-                          GmresState *st, int m, GmresState *poll, const GmPatchSrc *ps)
+                          GmresState *st, int m, GmresHead *poll, const GmPatchSrc *ps)
 {
-    if (ps && ps->S != 5 && ps->S != 9) return hipErrorInvalidValue;
-    const auto run = [&](auto EPT) {
-        orth_passes<EPT()>(c, w, dinv, V, ldv, part, st, m, poll, ps);
-        return true;
-    };
-    if (!dispatch_value<5, 6, 8>(orth_ept(c), false, run)) run(std::integral_constant<int, 4>{});  // (any other: 4)
+    const int ept = orth_ept(c);
+    const int64_t n = c->nl, lo = c->skip_lo, chunk = (int64_t)kRedThreads * ept;
+    const int nb = (int)((n + chunk - 1) / chunk);
+    const bool mr = multi_rank(c);
+    const hipError_t bad = with_patch_src(ps, [&](auto S, const GmPatchSrc &src) {
+        with_ept(ept, [&](auto E) {
+            hipLaunchKernelGGL((k_gm_pass1<kGmBatch, E(), S()>), dim3(nb), dim3(kRedThreads), 0, c->stream, w, dinv, V,
+                               n, ldv, lo, part, nb, st, src);
+        });
+    });
+    if (bad != hipSuccess) return bad;
+    // the projections' sums: a block per projection, so not launch_summed's shape
+    hipLaunchKernelGGL(k_gm_dots_fin_mb, dim3(m + 1), dim3(kRedThreads), 0, c->stream, part, nb, st, mr ? 1 : 0);
+    if (mr) {
+        comm_allreduce(c, st->red, m + 1);
+        hipLaunchKernelGGL(k_gm_dots_fin, dim3(1), dim3(1024), 0, c->stream, st);
+    }
+    with_ept(ept, [&](auto E) {
+        hipLaunchKernelGGL((k_gm_pass2<kGmBatch2, E()>), dim3(nb), dim3(kRedThreads), 0, c->stream, w, V, n, ldv, lo,
+                           part, st);
+    });
+    launch_summed(c, st->red, 1, poll, [&](int mode, GmresHead *slot) {
+        hipLaunchKernelGGL(k_gm_norm_fin, dim3(1), dim3(1024), 0, c->stream, part, nb, st, mode, slot);
+    });
     return hipGetLastError();
 }
 
-hipError_t launch_gm_update(cdfem_ctx *c, double *x, const double *V, int64_t ldv, GmresState *st, GmresState *poll)
+hipError_t launch_gm_update(cdfem_ctx *c, double *x, const double *V, int64_t ldv, GmresState *st, GmresHead *poll)
 {
     const int nb = gmres_blocks(c->nl);
     hipLaunchKernelGGL(k_gm_solve_y, dim3(1), dim3(kRedThreads), 0, c->stream, st);

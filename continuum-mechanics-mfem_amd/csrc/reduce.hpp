@@ -10,7 +10,7 @@
 
 namespace cdfem {
 
-constexpr int kRedThreads = 256;
+// (kRedThreads, the block of these reductions: krylov_host.hpp, whose grid rule needs it without HIP)
 
 __device__ inline double wave_sum(double v)
 {

@@ -404,9 +404,8 @@ void solve_cg(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, doub
 }
 
 // PETSc KSPGMRES(m) + left Jacobi on the constrained operator (gmres.hip).  One host sync per
-// restart cycle plus a lag-one poll inside the cycle: step j + 1 is queued before the host waits
-// for step j's flags, so the GPU never idles on the host; a step queued past the end of a cycle
-// costs one wasted operator apply (its GMRES kernels exit at entry).
+// restart cycle plus the lag-one poll (LagPoll, krylov_host.hpp) inside the cycle: a step queued past
+// the end of a cycle costs one wasted operator apply (its GMRES kernels exit at entry).
 void solve_gmres(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, double *dX, cdfem_solver_result &res)
 {
     const int m = p.restart > 0 ? p.restart : 30;
@@ -418,24 +417,22 @@ void solve_gmres(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, d
         c->d_gm.alloc((size_t)(m + 1) * ldv);
         c->d_gm_part.alloc((size_t)(m + 1) * nb);
     }
-    if (!c->d_gmst) {
-        c->d_gmst.alloc(1);
-        // poll slots: 0 for the cycle start / end, 1 + j for inner step j (each step its own slot, so a
-        // host check reads exactly the state of the step it waited for: ranks decide alike)
-        c->h_gmpoll.alloc(kGmMaxRestart + 1);
-        for (auto &e : c->gm_ev) e.create(false);
-    }
+    // poll slots: 0 for the cycle start / end, 1 + j for inner step j (each step its own slot, so a
+    // host check reads exactly the state of the step it waited for: ranks decide alike)
+    krylov_state_alloc(c->d_gmst, c->h_gmpoll, kGmMaxRestart + 1, c->gm_ev);
     const bool ilu = p.pc == CDFEM_PC_ILU;
     const double *dinv = resolve_pc(c, p);
     double *x = c->d_w[2], *w = c->d_w[4], *V = c->d_gm, *part = c->d_gm_part;
-    GmresState *st = c->d_gmst, *poll = c->h_gmpoll;
-    // the step's last scalar kernel has written poll[slot] (post_poll in gmres.hip); the event
-    // marks its completion for the host.  (Measured alternatives, profiles/r03/ab_c2_gmres_poll.txt:
-    // spinning on a stamp in pinned memory, 392.2 / 392.0 against 392.3 us per C2 step; polling every
-    // 2 / 4 / 30 steps, 390.3 / 388.4 / 388.0 against 391.5: the host wait is not on the critical path.)
-    auto post = [&](int slot) { HIPCHK(hipEventRecord(c->gm_ev[slot], c->stream)); };
-    auto wait = [&](int slot) -> const GmresState & {
-        HIPCHK(hipEventSynchronize(c->gm_ev[slot]));
+    GmresState *st = c->d_gmst;
+    GmresHead *poll = c->h_gmpoll;
+    // the step's last scalar kernel has written poll[slot] (post_head); the event marks its completion
+    // for the host.  (Measured alternatives, profiles/r03/ab_c2_gmres_poll.txt: spinning on a stamp in
+    // pinned memory, 392.2 / 392.0 against 392.3 us per C2 step; polling every 2 / 4 / 30 steps, 390.3 /
+    // 388.4 / 388.0 against 391.5: the host wait is not on the critical path.)
+    auto post = [&](int ev) { HIPCHK(hipEventRecord(c->gm_ev[ev], c->stream)); };
+    auto sync = [&](int ev) { HIPCHK(hipEventSynchronize(c->gm_ev[ev])); };
+    auto wait = [&](int slot) -> const GmresHead & {  // the synchronous checks of slot 0, on event 0
+        sync(slot);
         return poll[slot];
     };
     // pass 1 forms A_c v_j from the patch buffer itself
@@ -443,24 +440,10 @@ void solve_gmres(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, d
     // gm_poll k (default 4): an event and a host check every k inner steps (and at a cycle's last step)
     // instead of every step: each event costs the GPU ~5 us before the next Mult (rocprofv3 trace gaps,
     // profiles/r06/ab_gmres_poll/; C2 step 181.3-182.8 -> 178.1-178.2 us at k = 4).  Every step's last
-    // scalar kernel posts the state head into its own slot poll[1 + j]; a check waits for the previous
-    // check's event and reads exactly that step's slot, never a later step's (on several ranks every rank
-    // must leave the loop at the same step: their collectives pair up).  Steps queued past the end of a
-    // cycle exit at entry; their Mult does not check: a cycle done at step s is posted by the next polled
-    // step q < s + k and read after step q + k is queued (solve_bicgstab's argument), so the Mult runs at
-    // most 2k - 1 times past the end of a converged cycle.
+    // scalar kernel posts the state head into its own slot poll[1 + j]; the Mult runs at most 2k - 1 times
+    // past the end of a converged cycle (LagPoll).
     const int pk = std::max(1, c->gm_poll);
-    int nposts = 0, last_posted = -1;
-    auto step_end = [&](int j, bool cycle_last) -> bool {  // true: the cycle is done, leave the step loop
-        if (!cycle_last && (j + 1) % pk != 0) return false;
-        post(nposts & 1);
-        const int prev = last_posted;
-        last_posted = j;
-        ++nposts;
-        if (nposts < 2 || prev < 0) return false;
-        HIPCHK(hipEventSynchronize(c->gm_ev[(nposts - 2) & 1]));  // the previous check's event
-        return poll[1 + prev].cycle_done != 0;                      // exactly its step's state
-    };
+    LagPoll lag(post, sync);
     const auto t0 = solve_begin(c);
     HIPCHK(hipMemsetAsync(x, 0, n * sizeof(double), c->stream));
     HIPCHK(launch_gm_init(c, st, m, p.max_iter));
@@ -492,10 +475,11 @@ void solve_gmres(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, d
             timed(c, CDFEM_K_ORTH, [&] {
                 HIPCHK(launch_gm_orth(c, ilu ? c->ilu.z : w, dinv, V, ldv, part, st, m, &poll[1 + j], gpb ? &src : nullptr));
             });
-            if (step_end(j, j == m - 1)) break;
+            if (j != m - 1 && (j + 1) % pk != 0) continue;
+            const int prev = lag.post(j);
+            if (prev >= 0 && poll[1 + prev].cycle_done) break;  // exactly that step's state
         }
-        nposts = 0;
-        last_posted = -1;
+        lag.reset();
         timed(c, CDFEM_K_UPDATE, [&] { HIPCHK(launch_gm_update(c, x, V, ldv, st, &poll[0])); });
         post(0);
         if (wait(0).done) break;
@@ -514,14 +498,10 @@ void solve_gmres(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, d
 // operator applies per iteration, no orthogonalisation.  The host queues iterations without waiting
 // for the device: every check_every-th iteration's last scalar kernel posts the head of the state into
 // the pinned slot (i / check_every) % kBcgsSlots, a function of the iteration number alone and so the
-// same on every rank, and the host reads a posted iteration's slot one check later, after the next
-// check_every iterations are queued (the lag-one poll of solve_gmres).  A slot is rewritten kBcgsSlots
-// checks later, after the host has read it, so a check reads the state of exactly the iteration it names;
-// the all-reduced sums make that state the same on every rank, so every rank leaves the loop at the same
-// iteration and their collectives pair up.  Past the stop every solver kernel exits at entry; the applies
-// do not check: a stop at iteration s is posted by the next polled iteration q < s + check_every and read
-// after iteration q + check_every is queued, so at most 2 check_every - 1 iterations, that is
-// 2 (2 check_every - 1) operator applies, run past the stop (and never more than max_iter iterations in all).
+// same on every rank, and the host reads a posted iteration's slot one check later (LagPoll,
+// krylov_host.hpp).  A slot is rewritten kBcgsSlots checks later, after the host has read it.  At most
+// 2 check_every - 1 iterations, that is 2 (2 check_every - 1) operator applies, run past the stop (and
+// never more than max_iter iterations in all).
 void solve_bicgstab(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, double *dX, cdfem_solver_result &res)
 {
     const int64_t n = c->nl;
@@ -531,17 +511,14 @@ void solve_bicgstab(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB
         c->d_bcgs.alloc((size_t)6 * ldv);
         c->d_bcgs_part.alloc((size_t)3 * nb);
     }
-    if (!c->d_bcst) {
-        c->d_bcst.alloc(1);
-        c->h_bcpoll.alloc(kBcgsSlots + 1);
-        for (auto &e : c->bc_ev) e.create(false);
-    }
+    krylov_state_alloc(c->d_bcst, c->h_bcpoll, kBcgsSlots + 1, c->bc_ev);
     const bool ilu = p.pc == CDFEM_PC_ILU;
     const double *dinv = resolve_pc(c, p);
     double *x = c->d_bcgs, *r = x + ldv, *rh = r + ldv, *pv = rh + ldv, *v = pv + ldv, *t = v + ldv;
     double *w = c->d_w[4], *part = c->d_bcgs_part;  // w: the apply's output (and ilu_apply's input)
-    BcgsState *st = c->d_bcst, *poll = c->h_bcpoll;
-    // k_bcgs_v / k_bcgs_t form A_c u from the patch buffer itself (GMRES's predicate)
+    BcgsState *st = c->d_bcst;
+    BcgsHead *poll = c->h_bcpoll;
+    // k_bcgs_v / k_bcgs_t form A_c u from the patch buffer itself
     const bool gpb = patch_mult(c, ilu);
     c->bcgs_src = gpb ? kBrick * c->p + 1 : 0;
     c->bcgs_diag = dinv ? 1 : 0;
@@ -570,9 +547,11 @@ void solve_bicgstab(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB
     timed(c, CDFEM_K_UPDATE, [&] {
         HIPCHK(launch_bcgs_init(c, b0, dinv, r, rh, part, st, p.rel_tol, p.abs_tol, p.max_iter, &poll[kBcgsSlots]));
     });
-    HIPCHK(hipEventRecord(c->bc_ev[0], c->stream));
-    HIPCHK(hipEventSynchronize(c->bc_ev[0]));
-    int nchecks = 0, prev_slot = -1;
+    auto post = [&](int ev) { HIPCHK(hipEventRecord(c->bc_ev[ev], c->stream)); };
+    auto sync = [&](int ev) { HIPCHK(hipEventSynchronize(c->bc_ev[ev])); };
+    post(0);  // the start slot, synchronously
+    sync(0);
+    LagPoll lag(post, sync);
     for (int i = 0; i < p.max_iter && !poll[kBcgsSlots].done; ++i) {
         const bool polled = (i + 1) % ce == 0;
         const int slot = (i / ce) % kBcgsSlots;
@@ -587,13 +566,8 @@ void solve_bicgstab(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB
                                  gpb ? &srcs : nullptr));
         });
         if (!polled) continue;
-        HIPCHK(hipEventRecord(c->bc_ev[nchecks & 1], c->stream));
-        const int prev = prev_slot;
-        prev_slot = slot;
-        ++nchecks;
-        if (prev < 0) continue;
-        HIPCHK(hipEventSynchronize(c->bc_ev[nchecks & 1]));  // the previous check's event
-        if (poll[prev].done) break;                           // exactly its iteration's state
+        const int prev = lag.post(slot);
+        if (prev >= 0 && poll[prev].done) break;  // exactly that iteration's state
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     solve_end(c, t0, res, x, dX, [&] {

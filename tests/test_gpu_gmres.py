@@ -207,3 +207,33 @@ def test_gmres_poll_interval_bitwise(gpu_ctx, structured, restart):
         assert jk["iterations"] == j1["iterations"]
     with pytest.raises(cdfem.CdfemError):
         gpu_ctx.set_option("gm_poll", 0)
+
+
+def test_gmres_restart_64_slots(gpu_ctx):
+    """The longest restart, GMRES(64): its inner steps post into the poll slots 1 .. 1 + 63, the whole pinned
+    buffer, whose stride is the size of the state's head.  The 8 x 8 x 8 p = 2 structured box (4,913 dofs, the
+    BOX8 system of test_gpu_solve_launches.py), Jacobi, tolerances 0, 70 steps (one full cycle and six steps),
+    polled every step, every 4th and once per cycle: the three solutions bitwise equal, 70 iterations each, and
+    the fixed-step bound of this file against the oracle, relative L2 <= 1e-11.  Nobody had measured 64
+    unrefined Gram-Schmidt steps against the oracle: the library of the parent commit (c239f2f) measured
+    1.0e-15 on this case (after the 70 steps the residual estimate is 1.5e-12 against 2e1 after ten, so both
+    iterates are the solution to rounding), and this library gives the parent's x bit for bit.  The parent
+    meets 1e-11, so that bound is asserted, not a multiple of the measured distance."""
+    om, Ac, Bo, B = _system(gpu_ctx, 3, 8, 2, 0.0, structured=True, seed=3)
+    assert om.nl == 4913
+    xo, io = O.gmres(Ac, Bo, dinv=1.0 / Ac.diag(), restart=64, rtol=0.0, atol=0.0, max_it=70)
+    out = {}
+    try:
+        for k in (1, 4, 64):
+            gpu_ctx.set_option("gm_poll", k)
+            out[k] = gpu_ctx.solve(B, method="gmres", pc="jacobi", restart=64, rel_tol=0.0, abs_tol=0.0, max_iter=70)
+    finally:
+        gpu_ctx.set_option("gm_poll", 4)
+    rel = {k: np.linalg.norm(x - xo) / np.linalg.norm(xo) for k, (x, _) in out.items()}
+    print("gmres(64) 70 steps, relative L2 against the oracle per gm_poll:", rel)
+    assert io["iterations"] == 70
+    for k in (1, 4, 64):
+        assert out[k][1]["iterations"] == 70 and not out[k][1]["converged"]
+    np.testing.assert_array_equal(out[4][0], out[1][0])
+    np.testing.assert_array_equal(out[64][0], out[1][0])
+    assert rel[1] <= 1e-11
