@@ -202,7 +202,8 @@ void require_mesh(cdfem_ctx *c)
 void require_pa(cdfem_ctx *c)
 {
     require_mesh(c);
-    if (!c->pa_ready && !c->fa_ready) throw StateError("no operator: call cdfem_pa_setup or cdfem_fa_setup");
+    if (!c->pa_ready && !c->fa_ready && !nl_jac_current(c))
+        throw StateError("no operator: call cdfem_pa_setup or cdfem_fa_setup");
 }
 
 // a communicator of more than one rank needs a declared partition: the z-slab of a structured box
@@ -769,6 +770,17 @@ static int simplex_rule_pts(const cdfem_ctx *c, int rule, const std::vector<doub
     return nq;
 }
 
+// quads / hexes: the 1D tables of a rule (CDFEM_RULE_NONLINEAR: after cdfem_nl_pa_setup)
+static const Rule1D &tensor_rule(const cdfem_ctx *c, int rule)
+{
+    if (rule == CDFEM_RULE_NONLINEAR) {
+        if (!c->heat.ready || !c->heat.tensor)
+            throw StateError("CDFEM_RULE_NONLINEAR: cdfem_nl_pa_setup has not been called");
+        return c->heat.rule;
+    }
+    return rule == CDFEM_RULE_LINEARFORM ? c->rule_lf : rule == CDFEM_RULE_ERROR ? c->rule_err : c->rule_op;
+}
+
 int cdfem_rule_size(cdfem_ctx *c, int rule, int *nq)
 {
     return guarded(c, [&] {
@@ -778,8 +790,7 @@ int cdfem_rule_size(cdfem_ctx *c, int rule, int *nq)
             *nq = simplex_rule_pts(c, rule, nullptr);
             return CDFEM_OK;
         }
-        const Rule1D &r = rule == CDFEM_RULE_LINEARFORM ? c->rule_lf : rule == CDFEM_RULE_ERROR ? c->rule_err
-                                                                                                 : c->rule_op;
+        const Rule1D &r = tensor_rule(c, rule);
         *nq = nq_of(c, r);
         return CDFEM_OK;
     });
@@ -813,8 +824,7 @@ int cdfem_quadrature_points(cdfem_ctx *c, int rule, double *xyz, int where)
             }
             return CDFEM_OK;
         }
-        const Rule1D &r = rule == CDFEM_RULE_LINEARFORM ? c->rule_lf : rule == CDFEM_RULE_ERROR ? c->rule_err
-                                                                                                 : c->rule_op;
+        const Rule1D &r = tensor_rule(c, rule);
         const size_t n = (size_t)c->ne * nq_of(c, r) * c->dim;
         DevBuf<double> tmp;
         if (where != CDFEM_DEVICE) tmp.alloc(n);
@@ -854,6 +864,7 @@ static int pa_setup_form(cdfem_ctx *c, const cdfem_form_coeffs *f)
             throw UnsupportedError("no PA apply kernel built for dim=" + std::to_string(c->dim) +
                                    " order=" + std::to_string(c->p));
         const unsigned kinds = f->kinds;
+        c->heat.jac_mf = false;  // the linear operator is the current one again
         c->kinds = kinds;
         c->ncomp = ((kinds & CDFEM_DIFFUSION) ? c->dim * (c->dim + 1) / 2 : 0) +
                    ((kinds & CDFEM_CONVECTION) ? c->dim : 0) + ((kinds & CDFEM_MASS) ? 1 : 0);
@@ -1080,10 +1091,11 @@ int cdfem_pa_diagonal(cdfem_ctx *c, double *diag, int where)
         if (c->fa_ready) {
             HIPCHK(launch_csr_diag(c, dd));
         } else {
-            HIPCHK(launch_diag_elem(c, c->d_Ye));
+            timed(c, CDFEM_K_DIAGONAL, [&] { HIPCHK(launch_diag_elem(c, c->d_Ye)); });
             HIPCHK(launch_e2l(c, c->d_Ye, nullptr, dd, false, 0));
         }
         dev_out(c, diag, where, dd, c->nl);
+        prof_collect(c);
         return CDFEM_OK;
     });
 }

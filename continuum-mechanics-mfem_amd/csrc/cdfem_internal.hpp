@@ -29,17 +29,7 @@
 namespace cdfem {
 
 constexpr int kLanes = 64;        // elements per element-block (= wavefront width)
-constexpr int kMaxD1 = 6;
-constexpr int kMaxQ1 = 8;
-
-// 1D tables for one quadrature rule: B[q][d] = phi_d(xi_q), G[q][d] = phi_d'(xi_q), points, weights
-struct Rule1D {
-    int d1 = 0, q1 = 0;
-    double B[kMaxQ1][kMaxD1] = {};
-    double G[kMaxQ1][kMaxD1] = {};
-    double pts[kMaxQ1] = {};
-    double wts[kMaxQ1] = {};
-};
+// (kMaxD1, kMaxQ1 and Rule1D, the 1D tables of one quadrature rule: ctx_state.hpp)
 
 // Product implementation of the 1D rules (independent of the oracle): basis.cpp
 void gll_nodes(int p, double *x);
@@ -588,6 +578,16 @@ hipError_t launch_nl_gradient(cdfem_ctx *c, const double *u);
 hipError_t launch_nl_finish(cdfem_ctx *c, double *R, const double *g, double *negR);
 // facet E-vector from the point values gq, then b = its per-dof sums in ascending facet order
 hipError_t launch_bdr_lf(cdfem_ctx *c, const double *gq, double *b);
+// the same form on quads and hexes, matrix-free (nl_tensor.hip): the spaces it is built for, its rule's points
+// per direction, and k_nl_tensor in mode 0 (Ye = the elements' shares of R(u)), 1 (of J(u) v; con: essential
+// entries of v read as 0) or 2 (of J(u)'s diagonal), Ye in the context's E-vector layout; u_old from c->heat
+bool nl_tensor_supported(int dim, int p);
+int nl_tensor_points_1d(int dim, int p);
+hipError_t launch_nl_tensor(cdfem_ctx *c, int mode, const double *u, const double *v, bool con, double *Ye,
+                            const KrylovState *st);
+// the matrix-free Jacobian of the nonlinear form is the current operator: every structured fast path of the
+// linear operator is off (they key on the mesh), and the launch points route to k_nl_tensor
+inline bool nl_jac_current(const cdfem_ctx *c) { return c->heat.jac_mf; }
 // the assembled operator's pattern on the device, built once per mesh (capi.hip; cdfem_fa_setup, cdfem_nl_gradient)
 void fa_ensure_pattern(cdfem_ctx *c);
 

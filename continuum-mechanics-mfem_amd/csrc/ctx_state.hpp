@@ -10,6 +10,18 @@
 
 namespace cdfem {
 
+constexpr int kMaxD1 = 6;
+constexpr int kMaxQ1 = 8;
+
+// 1D tables for one quadrature rule: B[q][d] = phi_d(xi_q), G[q][d] = phi_d'(xi_q), points, weights
+struct Rule1D {
+    int d1 = 0, q1 = 0;
+    double B[kMaxQ1][kMaxD1] = {};
+    double G[kMaxQ1][kMaxD1] = {};
+    double pts[kMaxQ1] = {};
+    double wts[kMaxQ1] = {};
+};
+
 // The assembled operator's pattern on the device (cdfem_fa_setup, once per mesh): CSR with sorted columns,
 // deterministic contribution lists, and the SELL-64 copy the SpMV streams.  A struct of its own so that the
 // setup builds one aside and moves it into the context whole: a refused setup leaves no half-built pattern.
@@ -39,8 +51,14 @@ struct FaDeviceState {
 // The nonlinear heat form and its Newton solve (cdfem_nl_setup, cdfem_bdr_set; nl_kernels.hip, newton.hip):
 // coefficients, the tables of the order 2p + 2 rule, the boundary facets with their rule and gather lists,
 // the Newton vectors (device-resident for a whole solve) and the history of the last solve.
+// On quad / hex meshes (cdfem_nl_pa_setup; nl_tensor.hip) the form is matrix-free: the tensor rule's 1D tables,
+// and the Jacobian as the state it was linearised at.
 struct NlState {
     bool ready = false;
+    bool tensor = false;                // set up by cdfem_nl_pa_setup (quads / hexes, matrix-free)
+    bool jac_mf = false;                // the matrix-free J(d_ulin) is the context's current operator
+    Rule1D rule;                        // tensor: Gauss-Legendre, p + 2 (quads) / p + 3 (hexes) points per direction
+    DevBuf<double> d_ulin;              // tensor: the linearisation state, a copy (the Newton loop updates d_u in place)
     double dt = 0.0, a0 = 0.0, a1 = 0.0, m0 = 0.0, m1 = 0.0, u_ref = 0.0;
     int nq = 0;                         // points of the order 2p + 2 rule
     std::vector<double> h_sxi;          // its points (reference coordinates)

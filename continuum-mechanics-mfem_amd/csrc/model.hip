@@ -19,7 +19,8 @@ void kernel_name(const cdfem_ctx *c, int k, char *buf, size_t n)
         return;
     }
     if (k != CDFEM_K_APPLY) throw UnsupportedError("kernel names: the operator apply only");
-    const char *name = c->fa_ready ? (c->lds_rows > 0 ? "k_sell_spmv_lds" : "k_sell_spmv")
+    const char *name = nl_jac_current(c) ? "k_nl_tensor"
+                       : c->fa_ready ? (c->lds_rows > 0 ? "k_sell_spmv_lds" : "k_sell_spmv")
                        : use_brick(c) ? "k_brick_cg"
                        : ho_uniform_elem(c) ? "k_hobrick_um"
                        : use_hobrick_cg(c) ? "k_hobrick_cg"
@@ -28,8 +29,28 @@ void kernel_name(const cdfem_ctx *c, int k, char *buf, size_t n)
     std::snprintf(buf, n, "%s", name);
 }
 
+// one k_nl_tensor launch in the Jacobian mode (nl_tensor.hip), per element, FMA = 2.  Fields: u, u - u(dof 0),
+// u - u_old and v.  Per thread (Q^2 of them): the x / y contractions of every dz plane (4 field sums and 2
+// derivative sums over dx, 8 accumulations per dy), the column's geometry, then per z point the z contraction
+// (11 sums over dz), the point (J from the column's faces, adj(J), det J, the two fluxes, the coefficients)
+// and the transposed z contraction (4 FMAs per dz); then per local dof the transposed x / y contraction.
+static double nl_jvp_flops(const cdfem_ctx *c)
+{
+    const double D = c->d1, Q = c->heat.rule.q1;
+    const bool d3 = c->dim == 3;
+    const double DZ = d3 ? D : 1.0, QZ = d3 ? Q : 1.0;
+    const double xy = DZ * D * (2.0 * 6 * D + 2.0 * 8 + D);            // (+ the D differences u - u(dof 0))
+    const double geo = d3 ? 2 * 3 * (2 + 6 + 8) + 3.0 : 2 * (2 + 6);
+    const double zc = 2.0 * (d3 ? 11 : 0) * DZ;
+    const double pt = d3 ? (12 * 2 + 27 + 5) + 2 * (2 * 18 + 3) + 30 : (4 + 3) + 2 * (2 * 8 + 2) + 24;
+    const double zt = 2.0 * (d3 ? 4 : 3) * DZ;
+    const double out = D * D * DZ * Q * (Q * 2.0 * 3 + 2.0 * 2);
+    return (Q * Q * (xy + geo + QZ * (zc + pt + zt)) + out) * (double)c->ne;
+}
+
 double kernel_flops(const cdfem_ctx *c, int k)
 {
+    if (k == CDFEM_K_APPLY && nl_jac_current(c)) return nl_jvp_flops(c);
     if (k != CDFEM_K_APPLY || c->fa_ready || c->dim != 3)
         throw UnsupportedError("kernel flops: the 3D partial-assembly apply only");
     // sum factorization, one element (pa_core.hpp elem_apply3d): per z plane the z contraction
@@ -101,6 +122,10 @@ double kernel_flops(const cdfem_ctx *c, int k)
 double kernel_bytes(const cdfem_ctx *c, int k)
 {
     const double nl = (double)c->nl, ne = (double)c->ne, nd = c->nd;
+    if (k == CDFEM_K_APPLY && nl_jac_current(c))
+        // the matrix-free Jacobian: u, u_old and v gathered (each L-dof once), the element map, the slot
+        // permutation, the vertices, the E-vector write; no point data
+        return 24.0 * nl + 4.0 * nd * ne + 4.0 * ne + 8.0 * c->nv * c->dim * ne + 8.0 * nd * ne;
     if (k == CDFEM_K_UPDATE && c->last_method == CDFEM_BICGSTAB) {
         // the five vector kernels of one BiCGStab iteration (bicgstab.hip): k_bcgs_p 4 N, k_bcgs_s 3 N,
         // k_bcgs_x 7 N doubles; k_bcgs_v and k_bcgs_t each write their vector and read rh (s) and the

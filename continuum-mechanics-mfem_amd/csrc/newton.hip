@@ -3,6 +3,8 @@
 // newton_petsc_solver.hpp:180-259).  Host-side orchestration only: the residual, the Jacobian's element
 // matrices and the boundary load are formed by nl_kernels.hip, the sums and the assembly by the kernels of the
 // linear paths (k_e2l, k_fa_gather, k_fa_eliminate, k_sell_fill), each linear solve by solve.hip's drivers.
+// On quads and hexes (cdfem_nl_pa_setup) the form is matrix-free: nl_tensor.hip's one kernel gives the residual,
+// and the Jacobian is a copy of u that the linear operator's launch points hand to the same kernel.
 //
 // Host / device traffic of one Newton iteration: the residual norm and the update norm (8 bytes each, after
 // a one-block reduction) and whatever the linear solver polls; u, R, dx and u_old never leave the device.
@@ -42,10 +44,26 @@ void require_simplex_one_rank(cdfem_ctx *c, const char *what)
     if (c->geom != 1) throw UnsupportedError(std::string(what) + " is implemented for simplex meshes");
 }
 
+// after cdfem_nl_setup (simplices) or cdfem_nl_pa_setup (quads / hexes), on one rank
 void require_nl(cdfem_ctx *c)
 {
-    require_simplex_one_rank(c, "the nonlinear heat form");
-    if (!c->heat.ready) throw StateError("cdfem_nl_setup has not been called");
+    require_mesh(c);
+    if (multi_rank(c)) throw UnsupportedError("the nonlinear heat form runs on one rank");
+    if (!c->heat.ready || c->heat.tensor != (c->geom == 0))
+        throw StateError(c->geom == 0 ? "cdfem_nl_pa_setup has not been called" : "cdfem_nl_setup has not been called");
+}
+
+// what both setup calls share: the coefficients, the Newton vectors, u_old = 0 and g = 0, an empty history
+void nl_init_state(cdfem_ctx *c, const cdfem_nl_heat_coeffs *k)
+{
+    NlState &S = c->heat;
+    for (DevBuf<double> *v : {&S.d_u, &S.d_R, &S.d_rhs, &S.d_dx, &S.d_uold, &S.d_g}) v->alloc(c->nl);
+    S.d_norm.alloc(1);
+    HIPCHK(hipMemsetAsync(S.d_uold, 0, c->nl * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(S.d_g, 0, c->nl * sizeof(double), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));  // (the callers' host tables die at scope exit)
+    S.dt = k->dt; S.a0 = k->a0; S.a1 = k->a1; S.m0 = k->m0; S.m1 = k->m1; S.u_ref = k->u_ref;
+    S.hist_res.clear(); S.hist_upd.clear(); S.hist_lin.clear();
 }
 
 // n doubles from src (host or device) into the device buffer dst
@@ -59,15 +77,32 @@ void copy_in(cdfem_ctx *c, double *dst, const double *src, int where, size_t n)
 // zeroed; negR (may be null) = -R
 void nl_residual(cdfem_ctx *c, const double *u, double *R, double *negR)
 {
-    HIPCHK(launch_nl_residual(c, u, c->d_Ye));
+    if (c->heat.tensor)
+        timed(c, CDFEM_K_NL_RESIDUAL, [&] { HIPCHK(launch_nl_tensor(c, 0, u, nullptr, false, c->d_Ye, nullptr)); });
+    else
+        HIPCHK(launch_nl_residual(c, u, c->d_Ye));
     HIPCHK(launch_e2l(c, c->d_Ye, nullptr, R, false, 0));
     HIPCHK(launch_nl_finish(c, R, c->heat.d_g, negR));
 }
 
 // J(u) becomes the assembled operator: the element matrices in k_simplex_elem's layout, then the full
 // assembly's own gather, elimination and SELL fill; what belonged to the previous operator is dropped
+// On quads and hexes nothing is assembled: J(u) becomes the current operator as a copy of u, which the launch
+// points of the linear operator hand to k_nl_tensor (launch_apply_st, launch_diag_elem)
 void nl_jacobian(cdfem_ctx *c, const double *u)
 {
+    if (c->heat.tensor) {
+        NlState &S = c->heat;
+        if (u != S.d_ulin.get())
+            HIPCHK(hipMemcpyAsync(S.d_ulin, u, c->nl * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->kinds = CDFEM_DIFFUSION | CDFEM_CONVECTION | CDFEM_MASS;
+        S.jac_mf = true;
+        c->pa_ready = false;  // (the linear operator's point data no longer describe the current operator)
+        c->fa_ready = false;
+        c->dinv_ready = false;
+        return;
+    }
     fa_ensure_pattern(c);
     HIPCHK(launch_nl_gradient(c, u));
     HIPCHK(launch_fa_assemble(c));
@@ -134,13 +169,36 @@ int cdfem_nl_setup(cdfem_ctx *c, const cdfem_nl_heat_coeffs *k)
         }
         upload(c, S.d_tab, tab);
         upload(c, S.d_edofs, c->h_dofs);
-        for (DevBuf<double> *v : {&S.d_u, &S.d_R, &S.d_rhs, &S.d_dx, &S.d_uold, &S.d_g}) v->alloc(c->nl);
-        S.d_norm.alloc(1);
-        HIPCHK(hipMemsetAsync(S.d_uold, 0, c->nl * sizeof(double), c->stream));
-        HIPCHK(hipMemsetAsync(S.d_g, 0, c->nl * sizeof(double), c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));  // tab dies at scope exit
-        S.dt = k->dt; S.a0 = k->a0; S.a1 = k->a1; S.m0 = k->m0; S.m1 = k->m1; S.u_ref = k->u_ref;
-        S.hist_res.clear(); S.hist_upd.clear(); S.hist_lin.clear();
+        nl_init_state(c, k);
+        S.tensor = false;
+        S.ready = true;
+        return CDFEM_OK;
+    });
+}
+
+int cdfem_nl_pa_setup(cdfem_ctx *c, const cdfem_nl_heat_coeffs *k)
+{
+    return guarded(c, [&] {
+        require_mesh(c);
+        if (multi_rank(c)) throw UnsupportedError("the nonlinear heat form runs on one rank");
+        if (c->geom != 0) throw UnsupportedError("simplex meshes take the assembled form: cdfem_nl_setup");
+        if (!nl_tensor_supported(c->dim, c->p))
+            throw UnsupportedError("the matrix-free nonlinear form is built for quads p = 1..3 and hexes p = 1, 2");
+        if (!k) throw ArgError("null coefficients");
+        if (!(k->dt > 0.0)) throw ArgError("dt must be positive");
+        NlState &S = c->heat;
+        S.ready = false;
+        if (S.jac_mf) {  // (a Jacobian of the previous coefficients is no operator any more)
+            S.jac_mf = false;
+            c->dinv_ready = false;
+        }
+        // IntRules.Get(geom, 2p + OrderW + 2) with OrderW = dim - 1 on the multilinear map: order 2p + 3 / 2p + 4,
+        // which MFEM's tensor Gauss-Legendre rules meet with p + 2 / p + 3 points per direction
+        S.rule = make_rule(c->p, nl_tensor_points_1d(c->dim, c->p));
+        S.nq = nq_of(c, S.rule);
+        S.d_ulin.alloc(c->nl);
+        nl_init_state(c, k);
+        S.tensor = true;
         S.ready = true;
         return CDFEM_OK;
     });
@@ -153,6 +211,7 @@ int cdfem_nl_set_old(cdfem_ctx *c, const double *u_old, int where)
         if (!u_old) throw ArgError("null vector");
         copy_in(c, c->heat.d_uold, u_old, where, c->nl);
         HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->heat.jac_mf) c->dinv_ready = false;  // the matrix-free J reads the current u_old
         return CDFEM_OK;
     });
 }
@@ -178,6 +237,7 @@ int cdfem_nl_residual(cdfem_ctx *c, const double *u, double *R, int where)
         nl_residual(c, du, dR, nullptr);
         dev_out(c, R, where, dR, c->nl);
         HIPCHK(hipStreamSynchronize(c->stream));
+        prof_collect(c);
         return CDFEM_OK;
     });
 }

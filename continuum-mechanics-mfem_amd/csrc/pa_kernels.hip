@@ -848,6 +848,7 @@ static bool diag_sf_kinds(cdfem_ctx *c, double *Ye)
 
 hipError_t launch_diag_elem(cdfem_ctx *c, double *Ye)
 {
+    if (nl_jac_current(c)) return launch_nl_tensor(c, 2, c->heat.d_ulin, nullptr, false, Ye, nullptr);
     const int d1 = c->rule_op.d1, q1 = c->rule_op.q1;
     bool done = false;
     if (d1 == q1 - 1) {  // the operators' Gauss n = p + 2 rules: sum-factorised, compile-time sizes
@@ -917,6 +918,7 @@ bool apply_supported(int dim, int p)
 // the kernel-side CG loop passes its state so a finished solve turns queued launches into no-ops
 hipError_t launch_apply_st(cdfem_ctx *c, const double *x, double *Ye, bool con, const KrylovState *st)
 {
+    if (nl_jac_current(c)) return launch_nl_tensor(c, 1, c->heat.d_ulin, x, con, Ye, st);  // J(u) x, matrix-free
     const int q1 = c->rule_op.q1;
     if (c->dim == 3) {  // the Gauss rule of p + 2 points; p = 3, 4: wave per element (ho_kernels.hip)
         if (c->p >= 3) return launch_apply_wpe(c, x, Ye, con, st);

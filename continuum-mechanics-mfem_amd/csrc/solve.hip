@@ -15,14 +15,19 @@
 
 namespace cdfem {
 
-bool use_brick(const cdfem_ctx *c) { return c->structured && brick_supported(c->dim, c->p) && brick_fits(c); }
+// (every structured path keys on the mesh: all of them are off while the nonlinear form's matrix-free
+// Jacobian is the current operator, nl_jac_current)
+bool use_brick(const cdfem_ctx *c)
+{
+    return c->structured && !nl_jac_current(c) && brick_supported(c->dim, c->p) && brick_fits(c);
+}
 
 // the high-order brick CG (3D p = 3, 4, affine box with constant coefficients: the Kronecker tile core on
 // 2^3-element blocks, brick_kernels.hip k_hobrick_cg, then the brick update); on several ranks a z-slab
 // of 2^3 blocks (round 6: the plane pack and exchange of the p = 2 brick CG, rank-local den sums)
 bool use_hobrick_cg(const cdfem_ctx *c)
 {
-    return c->ho_brick != 0 && c->structured && c->qlay == 1 && c->hb_nblk > 0 && tile_kron(c) && tile_den_ok(c) &&
+    return c->ho_brick != 0 && c->structured && !nl_jac_current(c) && c->qlay == 1 && c->hb_nblk > 0 && tile_kron(c) && tile_den_ok(c) &&
            (!multi_rank(c) || (c->part_mode == 1 && c->hb_ez == kHoBrickEdge)) && !c->fa_ready && brick_fits(c);
 }
 bool use_brick_cg(const cdfem_ctx *c) { return use_brick(c) || use_hobrick_cg(c); }
@@ -343,7 +348,7 @@ void solve_cg(cdfem_ctx *c, const cdfem_solver_params &p, const double *dB, doub
     double *red = c->d_state->red;  // device scalars awaiting the all-reduce (multi-rank)
     // high order on a structured box, one rank: den from the apply's E-vector, E->L fused into the
     // update (ho_kernels.hip k_apply3d_tile<DEN>, vec_kernels.hip k_e2l_box<UPD>)
-    const bool fused = !mr && !c->fa_ready && c->cg_fused && tile_den_ok(c) && e2l_box_ok(c) &&
+    const bool fused = !mr && !c->fa_ready && !nl_jac_current(c) && c->cg_fused && tile_den_ok(c) && e2l_box_ok(c) &&
                        c->nl < ((int64_t)1 << 31);  // the flat update's fast division is exact below 2^31
     if (fused && !c->d_tpart) c->d_tpart.alloc(tile_den_blocks(c, true));
     // direction fold (ho_dfold): apply j forms d_j = z + beta d_{j-1} into the other direction buffer
@@ -601,7 +606,8 @@ void ensure_dinv(cdfem_ctx *c)
     // pa_uniform_diag: the class table of a uniform p = 2 box, checked against the vector on the device.
     // Several ranks keep it only if every rank's check passed (each picks a class's entry at the same
     // (x, y) of a shared plane, so the ranks' copies of the plane stay bitwise equal).
-    HIPCHK(setup_uniform_diag(c));
+    if (nl_jac_current(c)) c->d_udiag.reset();  // (J(u)'s diagonal has no classes)
+    else HIPCHK(setup_uniform_diag(c));
     if (multi_rank(c)) {
         double all = c->d_udiag ? 1.0 : 0.0;
         host_allreduce(c, &all, 1);

@@ -33,6 +33,7 @@ _PCS = {"none": PC_NONE, "jacobi": PC_JACOBI, "ilu": PC_ILU}
 RULE_OPERATOR, RULE_LINEARFORM, RULE_ERROR, RULE_DIFFUSION, RULE_CONVECTION, RULE_MASS = 0, 1, 2, 3, 4, 5
 RULE_NONLINEAR = 6
 K_APPLY, K_E2L, K_UPDATE, K_DIRECTION, K_ORTH = 0, 1, 2, 3, 4
+K_NL_RESIDUAL, K_DIAGONAL = 5, 6
 
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_NOT_CONVERGED, ERR_COMM = range(7)
 
@@ -163,6 +164,7 @@ def _declare(L):
         "cdfem_gmsh_sizes": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(i64)]),
         "cdfem_gmsh_mesh": (C.c_int, [C.c_char_p, C.c_int, _dp, _ip, _ip, _dp]),
         "cdfem_nl_setup": (C.c_int, [vp, C.POINTER(NlHeatCoeffs)]),
+        "cdfem_nl_pa_setup": (C.c_int, [vp, C.POINTER(NlHeatCoeffs)]),
         "cdfem_nl_set_old": (C.c_int, [vp, vp, C.c_int]),
         "cdfem_nl_set_rhs": (C.c_int, [vp, vp, C.c_int]),
         "cdfem_nl_residual": (C.c_int, [vp, vp, vp, C.c_int]),
@@ -625,6 +627,13 @@ class Context:
         """Backward-Euler quasi-linear heat form: a(u) = a0 + a1 (u - u_ref), m(u) = m0 + m1 (u - u_ref)."""
         k = NlHeatCoeffs(float(dt), float(a0), float(a1), float(m0), float(m1), float(u_ref))
         self._chk(self.L.cdfem_nl_setup(self.h, C.byref(k)))
+        return self
+
+    def nl_pa_setup(self, dt, a0, a1, m0, m1, u_ref=0.0):
+        """The same form on a quad / hex mesh, matrix-free: nl_gradient(u) then makes J(u) the current operator
+        of mult, diagonal and solve, and the other nl_* / newton_solve* methods work as on simplices."""
+        k = NlHeatCoeffs(float(dt), float(a0), float(a1), float(m0), float(m1), float(u_ref))
+        self._chk(self.L.cdfem_nl_pa_setup(self.h, C.byref(k)))
         return self
 
     def nl_set_old(self, u_old, where=HOST):

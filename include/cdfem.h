@@ -57,9 +57,11 @@ enum { CDFEM_PC_NONE = 0, CDFEM_PC_JACOBI = 1, CDFEM_PC_ILU = 2 };
  * MFEM's tabulated rules: DIFFUSION order 2p - 2, CONVECTION and MASS order 2p (OPERATOR refused). */
 enum { CDFEM_RULE_OPERATOR = 0, CDFEM_RULE_LINEARFORM = 1, CDFEM_RULE_ERROR = 2, CDFEM_RULE_DIFFUSION = 3,
        CDFEM_RULE_CONVECTION = 4, CDFEM_RULE_MASS = 5,
-       CDFEM_RULE_NONLINEAR = 6 /* simplices, after cdfem_nl_setup: the nonlinear heat form's rule, order 2p + 2 */ };
+       CDFEM_RULE_NONLINEAR = 6 /* after cdfem_nl_setup / cdfem_nl_pa_setup: the nonlinear heat form's rule */ };
 /* kernel ids for cdfem_profile_read */
 enum { CDFEM_K_APPLY = 0, CDFEM_K_E2L = 1, CDFEM_K_UPDATE = 2, CDFEM_K_DIRECTION = 3, CDFEM_K_ORTH = 4,
+       CDFEM_K_NL_RESIDUAL = 5, CDFEM_K_DIAGONAL = 6, /* profiling slots: cdfem_nl_pa_setup's residual kernel;
+                                                          the element part of cdfem_pa_diagonal */
        CDFEM_K_COUNT = 8 };
 
 int cdfem_abi_version(void);
@@ -255,6 +257,25 @@ int cdfem_nl_set_old(cdfem_ctx *ctx, const double *u_old, int where);
 int cdfem_nl_set_rhs(cdfem_ctx *ctx, const double *g, int where);
 int cdfem_nl_residual(cdfem_ctx *ctx, const double *u, double *R, int where);
 int cdfem_nl_gradient(cdfem_ctx *ctx, const double *u, int where);
+
+/* quad / hex meshes (cdfem_mesh_upload), one rank: the same form as cdfem_nl_setup, matrix-free.
+ * CDFEM_ERR_UNSUPPORTED on a simplex mesh, on more than one rank and outside quads p = 1..3 and hexes p = 1, 2
+ * (the orders of the simplex form); CDFEM_ERR_ARG for null coefficients or dt <= 0.  R and J v are those above;
+ * the geometry is the multilinear map of the element's 2^dim vertices, evaluated at every point.
+ * The rule is the same IntRules.Get(geom, 2p + OrderW + 2).  For the multilinear Qk geometry MFEM's OrderW() is
+ * order * dim - 1 (1 on quads, 2 on hexes), so the rule order is 2p + 3 / 2p + 4; MFEM builds square and cube
+ * rules as tensor Gauss-Legendre with (order | 1) / 2 + 1 points per direction: p + 2 on quads, p + 3 on hexes,
+ * one more than the operator rule.  (Derived from MFEM's sources, not pinned against an MFEM run: DESIGN 2.)
+ * CDFEM_RULE_NONLINEAR reports it: (p + 2)^2 / (p + 3)^3 points, q lexicographic with qx fastest.
+ * Afterwards cdfem_nl_set_old, cdfem_nl_set_rhs, cdfem_nl_residual, cdfem_newton_solve and
+ * cdfem_newton_history behave as on simplices (g any L-vector; cdfem_bdr_* stays simplex-only).
+ * cdfem_nl_gradient assembles nothing: it keeps a copy of u and makes J(u) the context's current operator, on
+ * which cdfem_pa_mult (constrained 0 / 1 / 2), cdfem_pa_diagonal and cdfem_solve (CG, GMRES, BiCGStab; no
+ * preconditioner or Jacobi; CDFEM_PC_ILU needs an assembled operator) act matrix-free, the constrained forms on
+ * the eliminated J(u); cdfem_fa_csr keeps CDFEM_ERR_STATE.  J reads the current u_old.  While J(u) is current
+ * no structured fast path runs and cdfem_kernel_name(CDFEM_K_APPLY) is "k_nl_tensor"; a later cdfem_pa_setup
+ * makes the linear operator current again.                                                             */
+int cdfem_nl_pa_setup(cdfem_ctx *ctx, const cdfem_nl_heat_coeffs *coeffs);
 
 /* replaces: NewtonPetscSolver::Solve (newton_petsc_solver.hpp:180-259; Input/petsc_nonlinear.opts for the
  * linear solve).  For iter = 0 .. max_iter - 1: R = residual(u), rn = ||R||_2; r0 = max(1, rn) on iteration 0;
