@@ -1700,8 +1700,15 @@ public:
     explicit BilinearForm(FiniteElementSpace *f) : Operator(f->GetVSize(), f->GetVSize()), fes_(f) {}
     // the form takes ownership of the integrator (MFEM semantics, :336-338)
     void AddDomainIntegrator(BilinearFormIntegrator *bfi) { integs_.emplace_back(bfi); }
-    // hexes/quads: partial assembly on the GPU; simplices: full assembly on the GPU
-    void SetAssemblyLevel(AssemblyLevel) {}
+    // simplices: full assembly on the GPU whatever the level.  Hexes / quads: partial assembly unless LEGACY or
+    // FULL is asked for explicitly, which assembles the CSR operator (cdfem_fa_setup_form: one rank, quads
+    // p = 1..4, hexes p = 1, 2); no call, PARTIAL, ELEMENT and NONE keep partial assembly
+    void SetAssemblyLevel(AssemblyLevel l) { level_ = l; level_set_ = true; }
+    // the resident operator is (or will be, once assembled) a CSR matrix: what ILU(0) needs
+    bool Assembled() const
+    {
+        return fes_->Simplex() || (level_set_ && (level_ == AssemblyLevel::LEGACY || level_ == AssemblyLevel::FULL));
+    }
     FiniteElementSpace *FESpace() const { return fes_; }
 
     void Assemble(int = 1)
@@ -1872,8 +1879,9 @@ private:
         }
         const cdfem_form_coeffs f{kinds, kappa, kq.empty() ? nullptr : kq.data(), kmq.empty() ? nullptr : kmq.data(),
                                   alpha, conv, cq.empty() ? nullptr : cq.data(), mass, mq.empty() ? nullptr : mq.data()};
-        // hexes / quads: partial assembly; simplices: full assembly (CSR on the GPU)
-        if (dev_->Simplex()) check(cdfem_fa_setup_form(ctx(), &f), ctx(), "cdfem_fa_setup_form");
+        // hexes / quads: partial assembly, or full assembly when SetAssemblyLevel asked for it; simplices: full
+        // assembly (CSR on the GPU)
+        if (dev_->Simplex() || Assembled()) check(cdfem_fa_setup_form(ctx(), &f), ctx(), "cdfem_fa_setup_form");
         else check(cdfem_pa_setup_form(ctx(), &f), ctx(), "cdfem_pa_setup_form");
     }
 
@@ -1882,6 +1890,8 @@ private:
     std::unique_ptr<DeviceSpace> dev_;
     std::unique_ptr<ConstrainedPAOperator> cop_;
     Vector XL_, BL_;  // FormLinearSystem's L-vectors, in HBM
+    AssemblyLevel level_ = AssemblyLevel::PARTIAL;
+    bool level_set_ = false;
 };
 using ParBilinearForm = BilinearForm;
 
@@ -2465,7 +2475,8 @@ private:
         solver_->SetMaxIter(maxit_ >= 0 ? maxit_ : std::stoi(Opt("ksp_max_it", "10000")));
         solver_->SetPrintLevel(print_);
         const FiniteElementSpace *fes = cop.Form()->FESpace();
-        const bool ilu_ok = fes->Simplex();  // assembled (one rank, or a general partition)
+        // assembled: a simplex space (one rank, or a general partition), or a quad / hex form at LEGACY / FULL
+        const bool ilu_ok = fes->Simplex() || cop.Form()->Assembled();
         std::string pc = Opt("pc_type", "");
         if (pc.empty()) {  // PETSc's default preconditioner: ILU on one rank, block Jacobi + ILU on several
             pc = ilu_ok ? (fes->NRanks() == 1 ? "ilu" : "bjacobi") : "jacobi";
@@ -2485,7 +2496,8 @@ private:
                 throw std::invalid_argument("unsupported block-Jacobi sub solver " + subksp + "/" + sub);
             if (pc == "ilu" && fes->NRanks() > 1)
                 throw std::invalid_argument("-pc_type ilu on several ranks (PETSc has no parallel ILU; use bjacobi)");
-            if (!ilu_ok) throw std::invalid_argument("-pc_type " + pc + " needs an assembled (simplex) operator");
+            if (!ilu_ok) throw std::invalid_argument("-pc_type " + pc + " needs an assembled operator (a simplex mesh, or "
+                                                "SetAssemblyLevel(AssemblyLevel::LEGACY) on quads / hexes)");
             solver_->SetPreconditioner(ilu_);
         } else if (pc != "none") {
             throw std::invalid_argument("unsupported -" + prefix_ + "pc_type " + pc);

@@ -37,6 +37,7 @@ struct Params {
     double kappa = 0.1, reaction = 1.0, c[3] = {1.0, -2.0, 0.5};
     int modes[3] = {3, 3, 3};
     string opts, mesh, cstr, mstr, mms = "sin";
+    bool fa = false;
 };
 
 // the circle variant's radial MMS, linear_convection_diffusion_2D_circle.cpp:140-215:
@@ -170,6 +171,8 @@ int main(int argc, char *argv[])
                                               "(the circle driver, 2D unit disk).");
     args.AddOption(&prm.opts, "-opts", "--petsc-options", "PETSc options file.");
     args.AddOption(&prm.print_level, "-pl", "--print-level", "Solver print level.");
+    args.AddOption(&prm.fa, "-fa", "--full-assembly", "-no-fa", "--no-full-assembly",
+                   "Assemble the CSR operator on quads / hexes (AssemblyLevel::LEGACY).");
     args.Parse();
     if (!args.Good()) {
         if (myid == 0) args.PrintUsage(cerr);
@@ -229,6 +232,7 @@ int main(int argc, char *argv[])
         a.AddDomainIntegrator(new DiffusionIntegrator(kappa_coeff));
         a.AddDomainIntegrator(new ConvectionIntegrator(convection_coeff));
         a.AddDomainIntegrator(new MassIntegrator(reaction_coeff));
+        if (prm.fa) a.SetAssemblyLevel(AssemblyLevel::LEGACY);
         a.Assemble();
 
         ParLinearForm b(&fespace);

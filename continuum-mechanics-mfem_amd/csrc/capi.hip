@@ -249,10 +249,18 @@ void fa_ensure_pattern(cdfem_ctx *c)
 {
     if (c->d_rowptr) return;
     // a multi-rank partition keeps the mesh order (its shared-dof exchange indexes L-vectors)
-    // dof coordinates for the geometric SpMV order (simplex geometry is on the host)
+    // dof coordinates for the geometric SpMV order (simplex geometry is on the host; quads and hexes keep
+    // theirs on the device alone, read back here once per mesh)
     std::vector<double> xyz;
-    if (!multi_rank(c) && (c->sell_mode == 3 || c->sell_mode >= 5) && !c->h_verts.empty())
-        xyz = simplex_dof_coords(c->dim, c->p, c->ne, c->nd, c->nl, c->h_verts, c->h_dofs);
+    if (!multi_rank(c) && (c->sell_mode == 3 || c->sell_mode >= 5)) {
+        if (c->geom == 0) {
+            std::vector<double> verts((size_t)c->ne * c->nv * c->dim);
+            HIPCHK(hipMemcpy(verts.data(), c->d_verts, verts.size() * sizeof(double), hipMemcpyDeviceToHost));
+            xyz = tensor_dof_coords(c->dim, c->p, c->ne, c->nd, c->nl, verts, c->h_dofs);
+        } else if (!c->h_verts.empty()) {
+            xyz = simplex_dof_coords(c->dim, c->p, c->ne, c->nd, c->nl, c->h_verts, c->h_dofs);
+        }
+    }
     FaPattern P = fa_build_pattern(c->h_dofs, c->ne, c->nd, c->nl,
                                    multi_rank(c) ? 0 : c->sell_mode, c->dim,
                                    xyz.empty() ? nullptr : xyz.data(), c->sell_window, c->spmv_lds,
@@ -910,8 +918,9 @@ static int pa_setup_form(cdfem_ctx *c, const cdfem_form_coeffs *f)
         HIPCHK(hipStreamSynchronize(c->stream));
         HIPCHK(setup_uniform_elem(c));  // pa_uniform: the common element matrix of a uniform box
         c->pa_ready = true;
-        c->fa_ready = false;
+        c->fa_ready = false;  // an assembled operator of this mesh is dropped (its pattern stays for the next one)
         c->dinv_ready = false;
+        ilu_free(c);
         HIPCHK(setup_ho_uniform_elem(c));  // ho_uniform: the same for the p = 3, 4 block CG (reads the flags above)
         return CDFEM_OK;
     });
@@ -1026,13 +1035,42 @@ int cdfem_mesh_upload_simplex(cdfem_ctx *c, int dim, int order, int ne, const do
     });
 }
 
+// quads and hexes (inside guarded): the element matrices of k_tensor_elem on the OPERATOR rule, then the
+// simplex pipeline.  The PA operator, the matrix-free Jacobian, the Jacobi scale and the ILU factors of the
+// previous operator are dropped; the pattern of an earlier assembly on this mesh is reused.
+static void fa_setup_tensor(cdfem_ctx *c, const cdfem_form_coeffs *f)
+{
+    if (!fa_tensor_supported(c->dim, c->p))
+        throw UnsupportedError("full assembly on tensor meshes is built for quads p = 1..4 and hexes p = 1, 2 (dim=" +
+                               std::to_string(c->dim) + " order=" + std::to_string(c->p) + ")");
+    if (multi_rank(c)) throw UnsupportedError("full assembly on quad and hex meshes runs on one rank");
+    fa_ensure_pattern(c);
+    // per-point coefficients at the OPERATOR rule's points (cdfem_quadrature_points' order)
+    const size_t neq = (size_t)c->ne * nq_of(c, c->rule_op);
+    const DevBuf<double> dk = upload_opt(c, f->kappa_q, neq), dkm = upload_opt(c, f->kappa_mat_q, neq * c->dim * (c->dim + 1) / 2);
+    const DevBuf<double> dc = upload_opt(c, f->conv_q, neq * c->dim), dm = upload_opt(c, f->mass_q, neq);
+    c->kinds = f->kinds;
+    HIPCHK(launch_tensor_elem(c, dk, dkm, f->kappa, f->alpha, f->conv, dc, dm, f->mass));
+    HIPCHK(launch_fa_assemble(c));
+    HIPCHK(launch_sell_fill(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->fa_ready = true;
+    c->pa_ready = false;
+    c->heat.jac_mf = false;
+    c->dinv_ready = false;
+    ilu_free(c);  // factors belong to the previous operator
+}
+
 static int fa_setup_form(cdfem_ctx *c, const cdfem_form_coeffs *f)
 {
     return guarded(c, [&] {
         require_mesh(c);
         check_form(c, f);
         const unsigned kinds = f->kinds;
-        if (c->geom != 1) throw UnsupportedError("full assembly is implemented for simplex meshes");
+        if (c->geom != 1) {
+            fa_setup_tensor(c, f);
+            return CDFEM_OK;
+        }
         fa_ensure_pattern(c);
         // per-point coefficients at the rule of their integrator
         const size_t nqd = (size_t)c->ne * c->nq_sd, nqc = (size_t)c->ne * c->nq_scm;

@@ -486,6 +486,9 @@ SellPlan sell_plan(int64_t nl, const int32_t *rowptr, const int32_t *cols, int m
 // dof coordinates of a simplex space (P1, P2, triangle P3 nodes; element-affine map), nl * dim
 std::vector<double> simplex_dof_coords(int dim, int p, int ne, int nd, int64_t nl, const std::vector<double> &verts,
                                        const std::vector<int32_t> &dofs);
+// dof coordinates of a quad / hex space: the multilinear map of the element's 2^dim vertices at the GLL nodes
+std::vector<double> tensor_dof_coords(int dim, int p, int ne, int nd, int64_t nl, const std::vector<double> &verts,
+                                      const std::vector<int32_t> &dofs);
 void sell_build(FaPattern &P, int64_t nl, const SellPlan &pl);
 FaPattern fa_build_pattern(const std::vector<int32_t> &elem_dofs, int ne, int nd, int64_t nl, int sell_mode,
                            int dim = 0, const double *dof_xyz = nullptr, int64_t sell_window = 0,
@@ -501,6 +504,11 @@ hipError_t dispatch_simplex(const cdfem_ctx *c, F &&f)
 }
 hipError_t launch_simplex_elem(cdfem_ctx *c, const double *kq, const double *kmq, double kappa, double alpha,
                                const double *conv, const double *cq, const double *mq, double mass);
+// the same on quads p = 1..4 and hexes p = 1, 2 (fa_tensor.hip): k_tensor_elem on the OPERATOR rule, element e the
+// mesh-order element (structured contexts too); per-point arrays in cdfem_quadrature_points(CDFEM_RULE_OPERATOR)'s order
+bool fa_tensor_supported(int dim, int p);
+hipError_t launch_tensor_elem(cdfem_ctx *c, const double *kq, const double *kmq, double kappa, double alpha,
+                              const double *conv, const double *cq, const double *mq, double mass);
 hipError_t launch_fa_assemble(cdfem_ctx *c);
 hipError_t launch_simplex_lf(cdfem_ctx *c, const double *fq, double *Ye);
 hipError_t launch_sell_fill(cdfem_ctx *c);

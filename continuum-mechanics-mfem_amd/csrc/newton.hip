@@ -101,6 +101,7 @@ void nl_jacobian(cdfem_ctx *c, const double *u)
         c->pa_ready = false;  // (the linear operator's point data no longer describe the current operator)
         c->fa_ready = false;
         c->dinv_ready = false;
+        ilu_free(c);  // (factors of an assembled linear operator on this mesh)
         return;
     }
     fa_ensure_pattern(c);
@@ -191,6 +192,11 @@ int cdfem_nl_pa_setup(cdfem_ctx *c, const cdfem_nl_heat_coeffs *k)
         if (S.jac_mf) {  // (a Jacobian of the previous coefficients is no operator any more)
             S.jac_mf = false;
             c->dinv_ready = false;
+        }
+        if (c->fa_ready) {  // an assembled linear operator of this mesh is dropped, as cdfem_pa_setup drops it
+            c->fa_ready = false;
+            c->dinv_ready = false;
+            ilu_free(c);
         }
         // IntRules.Get(geom, 2p + OrderW + 2) with OrderW = dim - 1 on the multilinear map: order 2p + 3 / 2p + 4,
         // which MFEM's tensor Gauss-Legendre rules meet with p + 2 / p + 3 points per direction

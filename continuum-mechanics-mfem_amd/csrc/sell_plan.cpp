@@ -195,6 +195,31 @@ std::vector<double> simplex_dof_coords(int dim, int p, int ne, int nd, int64_t n
     return xyz;
 }
 
+std::vector<double> tensor_dof_coords(int dim, int p, int ne, int nd, int64_t nl, const std::vector<double> &verts,
+                                      const std::vector<int32_t> &dofs)
+{
+    const int d1 = p + 1, nv = 1 << dim;
+    if (p < 1 || p >= kMaxD1 || nd != (dim == 3 ? d1 * d1 * d1 : d1 * d1))
+        throw std::runtime_error("tensor_dof_coords: unsupported element");
+    double gll[kMaxD1];
+    gll_nodes(p, gll);
+    std::vector<double> xyz((size_t)nl * dim, 0.0);
+    for (int e = 0; e < ne; ++e) {
+        const double *V = &verts[(size_t)e * nv * dim];
+        for (int l = 0; l < nd; ++l) {
+            const double xi[3] = {gll[l % d1], gll[(l / d1) % d1], dim == 3 ? gll[l / (d1 * d1)] : 0.0};
+            const int64_t g = dofs[(size_t)e * nd + l];
+            for (int k = 0; k < dim; ++k) xyz[(size_t)g * dim + k] = 0.0;
+            for (int v = 0; v < nv; ++v) {  // lexicographic vertices: bit m of v = position along axis m
+                double N = 1.0;
+                for (int m = 0; m < dim; ++m) N *= ((v >> m) & 1) ? xi[m] : 1.0 - xi[m];
+                for (int k = 0; k < dim; ++k) xyz[(size_t)g * dim + k] += N * V[v * dim + k];
+            }
+        }
+    }
+    return xyz;
+}
+
 // geometric order: dof coordinates quantised to the mean dof spacing h = (box volume / nl)^(1/dim)
 // and sorted by (z cell, y cell, x); ties by mesh index (deterministic)
 std::vector<int32_t> geometric_order(int64_t nl, int dim, const double *xyz)

@@ -16,10 +16,10 @@
 namespace cdfem {
 
 // (every structured path keys on the mesh: all of them are off while the nonlinear form's matrix-free
-// Jacobian is the current operator, nl_jac_current)
+// Jacobian is the current operator, nl_jac_current, or an assembled one, fa_ready: the SpMV runs then)
 bool use_brick(const cdfem_ctx *c)
 {
-    return c->structured && !nl_jac_current(c) && brick_supported(c->dim, c->p) && brick_fits(c);
+    return c->structured && !nl_jac_current(c) && !c->fa_ready && brick_supported(c->dim, c->p) && brick_fits(c);
 }
 
 // the high-order brick CG (3D p = 3, 4, affine box with constant coefficients: the Kronecker tile core on
@@ -606,7 +606,7 @@ void ensure_dinv(cdfem_ctx *c)
     // pa_uniform_diag: the class table of a uniform p = 2 box, checked against the vector on the device.
     // Several ranks keep it only if every rank's check passed (each picks a class's entry at the same
     // (x, y) of a shared plane, so the ranks' copies of the plane stay bitwise equal).
-    if (nl_jac_current(c)) c->d_udiag.reset();  // (J(u)'s diagonal has no classes)
+    if (nl_jac_current(c) || c->fa_ready) c->d_udiag.reset();  // (J(u)'s diagonal has no classes; the CSR's feeds no brick kernel)
     else HIPCHK(setup_uniform_diag(c));
     if (multi_rank(c)) {
         double all = c->d_udiag ? 1.0 : 0.0;

@@ -570,7 +570,10 @@ class Context:
 
     def fa_setup(self, kinds=DIFFUSION | CONVECTION | MASS, kappa=1.0, alpha=1.0, conv=None, mass=1.0,
                  kappa_q=None, conv_q=None, mass_q=None, kmat_q=None):
-        """Full assembly (CSR on the GPU) of the same form; simplex meshes."""
+        """Full assembly (CSR on the GPU) of the same form: simplex meshes (per-point arrays on the rule of their
+        integrator), and on one rank quads of order 1..4 and hexes of order 1, 2 (per-point arrays at the
+        RULE_OPERATOR points, as for pa_setup).  mult, diagonal, form_linear_system and solve then run on the CSR
+        operator, fa_csr exports it, and pc="ilu" is available to gmres and bicgstab."""
         f, keep = self._form(kinds, kappa, alpha, conv, mass, kappa_q, kmat_q, conv_q, mass_q)
         self._chk(self.L.cdfem_fa_setup_form(self.h, C.byref(f)))
         return self

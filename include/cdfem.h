@@ -138,7 +138,7 @@ typedef struct {
 } cdfem_form_coeffs;
 int cdfem_pa_setup_form(cdfem_ctx *ctx, const cdfem_form_coeffs *form);
 
-/* ---- full assembly on simplex meshes (BASELINE config C4: unstructured tetrahedra) -------------
+/* ---- full assembly: simplex meshes (BASELINE config C4: unstructured tetrahedra), quads and hexes ----
  * replaces: the same ParMesh / H1_FECollection(p, dim) / ParFiniteElementSpace calls on a triangle
  * or tetrahedral mesh (gmsh input, Input/input_2d.yaml:1), and ParBilinearForm::Assemble +
  * FormLinearSystem -> HypreParMatrix (linear_convection_diffusion_2D.cpp:339,349-351) whose CSR
@@ -155,7 +155,17 @@ int cdfem_pa_setup_form(cdfem_ctx *ctx, const cdfem_form_coeffs *form);
  * mass_q on CDFEM_RULE_MASS (cdfem_rule_size / cdfem_quadrature_points);
  * assembles A (CSR, columns sorted) and the eliminated matrix of FormLinearSystem on the GPU.
  * Afterwards cdfem_pa_mult / cdfem_pa_diagonal / cdfem_form_linear_system / cdfem_solve run on the
- * CSR operator.  cdfem_fa_csr exports it (rowptr n+1, cols/vals nnz; pass NULLs to query nnz).   */
+ * CSR operator.  cdfem_fa_csr exports it (rowptr n+1, cols/vals nnz; pass NULLs to query nnz).
+ * Quad and hex meshes (cdfem_mesh_upload): cdfem_fa_setup assembles the same CSR operator, MFEM's default
+ * Assemble() (full assembly, :339), on quads of order 1..4 and hexes of order 1, 2, on one rank (other orders
+ * and a communicator of several ranks: CDFEM_ERR_UNSUPPORTED).  The three integrators share the one
+ * CDFEM_RULE_OPERATOR rule there (Gauss-Legendre, p + 1 points per direction on quads, p + 2 on hexes), and
+ * every per-point array (kappa_q, kappa_mat_q, conv_q, mass_q) is sampled at its points, in the order
+ * cdfem_quadrature_points(CDFEM_RULE_OPERATOR) returns, as for cdfem_pa_setup.  The assembled operator replaces
+ * a partial-assembly one on the same context and the other way round (a later cdfem_pa_setup or
+ * cdfem_nl_pa_setup drops it, with its Jacobi scale and ILU(0) factors; the pattern is kept for the next
+ * cdfem_fa_setup).  On a context declared structured the solves then run the SpMV, not the brick kernels, and
+ * CDFEM_PC_ILU becomes available to GMRES and BiCGStab as on simplices.                                   */
 int cdfem_mesh_upload_simplex(cdfem_ctx *ctx, int dim, int order, int ne, const double *elem_verts,
                               int64_t nldofs, const int32_t *elem_dofs, int n_ess, const int32_t *ess_dofs);
 int cdfem_fa_setup(cdfem_ctx *ctx, unsigned kinds, double kappa, const double *kappa_q, double alpha,
@@ -667,7 +677,8 @@ int cdfem_partition_rcb(int dim, int ne, int nv, const double *elem_verts, int n
  * "sell_order" = mode: 0 mesh order + global length sort, 1 natural + windows, 2 reverse
  * Cuthill-McKee + windows, 3 auto (the mesh order when banded, else the geometric order when xyz is
  * given and banded, else RCM + global when it halves the bandwidth), 4 RCM + global, 5 geometric +
- * global).  xyz: nl * dim dof coordinates or NULL (cdfem_fa_setup passes the simplex space's nodes).
+ * global).  xyz: nl * dim dof coordinates or NULL (cdfem_fa_setup passes the space's nodes: the simplex
+ * space's, or the multilinear map at the GLL nodes on quads and hexes).
  * perm[space row] = mesh row; info[0..6] = base order (1 natural, 2 RCM, 3 geometric), window rows
  * (0: global length sort), max |column - row| in the space order, natural bandwidth, RCM bandwidth
  * (0 if not computed), stored SELL entries / nnz * 1e6, geometric bandwidth (0 if not computed).
