@@ -783,7 +783,7 @@ static const Rule1D &tensor_rule(const cdfem_ctx *c, int rule)
 {
     if (rule == CDFEM_RULE_NONLINEAR) {
         if (!c->heat.ready || !c->heat.tensor)
-            throw StateError("CDFEM_RULE_NONLINEAR: cdfem_nl_pa_setup has not been called");
+            throw StateError("CDFEM_RULE_NONLINEAR: neither cdfem_nl_pa_setup nor cdfem_nl_fa_setup has been called");
         return c->heat.rule;
     }
     return rule == CDFEM_RULE_LINEARFORM ? c->rule_lf : rule == CDFEM_RULE_ERROR ? c->rule_err : c->rule_op;

@@ -593,6 +593,13 @@ bool nl_tensor_supported(int dim, int p);
 int nl_tensor_points_1d(int dim, int p);
 hipError_t launch_nl_tensor(cdfem_ctx *c, int mode, const double *u, const double *v, bool con, double *Ye,
                             const KrylovState *st);
+// the same form with the Jacobian assembled (nl_fa_tensor.hip): the spaces it is built for, the doubles of the
+// point state c->heat.d_jq, and d_Ee = the element matrices of J(u) (k_nl_tensor_point, then k_nl_tensor_elem)
+bool nl_fa_tensor_supported(int dim, int p);
+size_t nl_fa_tensor_state_size(const cdfem_ctx *c);
+hipError_t launch_nl_tensor_elem(cdfem_ctx *c, const double *u);
+// the facet E-vector of the boundary linear form on quad / hex faces (k_bdr_lf_tensor; launch_bdr_lf gathers it)
+hipError_t launch_bdr_lf_tensor(cdfem_ctx *c, const double *gq);
 // the matrix-free Jacobian of the nonlinear form is the current operator: every structured fast path of the
 // linear operator is off (they key on the mesh), and the launch points route to k_nl_tensor
 inline bool nl_jac_current(const cdfem_ctx *c) { return c->heat.jac_mf; }

@@ -52,13 +52,16 @@ struct FaDeviceState {
 // coefficients, the tables of the order 2p + 2 rule, the boundary facets with their rule and gather lists,
 // the Newton vectors (device-resident for a whole solve) and the history of the last solve.
 // On quad / hex meshes (cdfem_nl_pa_setup; nl_tensor.hip) the form is matrix-free: the tensor rule's 1D tables,
-// and the Jacobian as the state it was linearised at.
+// and the Jacobian as the state it was linearised at.  cdfem_nl_fa_setup (nl_fa_tensor.hip) keeps the residual
+// matrix-free and assembles the Jacobian into the full assembly's CSR, through the point state d_jq.
 struct NlState {
     bool ready = false;
-    bool tensor = false;                // set up by cdfem_nl_pa_setup (quads / hexes, matrix-free)
+    bool tensor = false;                // set up by cdfem_nl_pa_setup or cdfem_nl_fa_setup (quads / hexes)
+    bool assembled = false;             // tensor, by cdfem_nl_fa_setup: cdfem_nl_gradient assembles J(u)
     bool jac_mf = false;                // the matrix-free J(d_ulin) is the context's current operator
     Rule1D rule;                        // tensor: Gauss-Legendre, p + 2 (quads) / p + 3 (hexes) points per direction
     DevBuf<double> d_ulin;              // tensor: the linearisation state, a copy (the Newton loop updates d_u in place)
+    DevBuf<double> d_jq;                // assembled: a(u), mu, grad u at the points, [nblk][nq][2 + dim][64] (kept across rebuilds)
     double dt = 0.0, a0 = 0.0, a1 = 0.0, m0 = 0.0, m1 = 0.0, u_ref = 0.0;
     int nq = 0;                         // points of the order 2p + 2 rule
     std::vector<double> h_sxi;          // its points (reference coordinates)
@@ -69,10 +72,14 @@ struct NlState {
     DevBuf<double> d_norm;              // [1] a norm's square on its way to the host
     // boundary linear form (cdfem_bdr_set)
     int nbf = 0, nqb = 0, nfd = 0;      // facets, points per facet, dofs per facet
+    int nqb1 = 0;                       // quad / hex faces: points per direction of the facet rule
     std::vector<int32_t> h_face_elem, h_face_local;
     std::vector<double> h_bxi;          // [dim + 1][nqb][dim] facet points in the element's reference coordinates
+                                        // (quad / hex faces: [2 dim][nqb][dim])
+    std::vector<double> h_bverts;       // quad / hex faces: [nbf][2^dim][dim] vertices of the facets' elements
     DevBuf<int32_t> d_face_elem, d_face_local;
     DevBuf<double> d_btab;              // phi [dim + 1][nqb][nfd] of the facet's dofs, w [nqb]
+                                        // (quad / hex faces: B [nqb1][p + 1], pts [nqb1], w [nqb1] of the 1D rule)
     DevBuf<int32_t> d_b_off, d_b_pos;   // per dof: its entries of the facet E-vector, ascending facet
     DevBuf<double> d_bYe, d_bgq;        // facet E-vector [nbf][nfd]; point values [nbf][nqb]
     // per-iteration history of the last Newton solve

@@ -4,7 +4,9 @@
 // matrices and the boundary load are formed by nl_kernels.hip, the sums and the assembly by the kernels of the
 // linear paths (k_e2l, k_fa_gather, k_fa_eliminate, k_sell_fill), each linear solve by solve.hip's drivers.
 // On quads and hexes (cdfem_nl_pa_setup) the form is matrix-free: nl_tensor.hip's one kernel gives the residual,
-// and the Jacobian is a copy of u that the linear operator's launch points hand to the same kernel.
+// and the Jacobian is a copy of u that the linear operator's launch points hand to the same kernel.  After
+// cdfem_nl_fa_setup the residual is the same kernel and the Jacobian is assembled as on simplices, its element
+// matrices by nl_fa_tensor.hip.
 //
 // Host / device traffic of one Newton iteration: the residual norm and the update norm (8 bytes each, after
 // a one-block reduction) and whatever the linear solver polls; u, R, dx and u_old never leave the device.
@@ -44,13 +46,43 @@ void require_simplex_one_rank(cdfem_ctx *c, const char *what)
     if (c->geom != 1) throw UnsupportedError(std::string(what) + " is implemented for simplex meshes");
 }
 
-// after cdfem_nl_setup (simplices) or cdfem_nl_pa_setup (quads / hexes), on one rank
+// after cdfem_nl_setup (simplices) or cdfem_nl_pa_setup / cdfem_nl_fa_setup (quads / hexes: heat.tensor, with
+// heat.assembled telling the two apart), on one rank
 void require_nl(cdfem_ctx *c)
 {
     require_mesh(c);
     if (multi_rank(c)) throw UnsupportedError("the nonlinear heat form runs on one rank");
     if (!c->heat.ready || c->heat.tensor != (c->geom == 0))
-        throw StateError(c->geom == 0 ? "cdfem_nl_pa_setup has not been called" : "cdfem_nl_setup has not been called");
+        throw StateError(c->geom == 0 ? "neither cdfem_nl_pa_setup nor cdfem_nl_fa_setup has been called"
+                                      : "cdfem_nl_setup has not been called");
+}
+
+// what the two quad / hex setups share (inside guarded): the refusals, the operator of the previous setup
+// dropped, the rule
+void nl_tensor_setup(cdfem_ctx *c, const cdfem_nl_heat_coeffs *k, const char *what)
+{
+    require_mesh(c);
+    if (multi_rank(c)) throw UnsupportedError("the nonlinear heat form runs on one rank");
+    if (c->geom != 0) throw UnsupportedError("simplex meshes take the assembled form: cdfem_nl_setup");
+    if (!nl_tensor_supported(c->dim, c->p) || !nl_fa_tensor_supported(c->dim, c->p))
+        throw UnsupportedError(std::string(what) + " is built for quads p = 1..3 and hexes p = 1, 2");
+    if (!k) throw ArgError("null coefficients");
+    if (!(k->dt > 0.0)) throw ArgError("dt must be positive");
+    NlState &S = c->heat;
+    S.ready = false;
+    if (S.jac_mf) {  // (a Jacobian of the previous coefficients is no operator any more)
+        S.jac_mf = false;
+        c->dinv_ready = false;
+    }
+    if (c->fa_ready) {  // an assembled operator of this mesh (linear, or a Jacobian) is dropped, as cdfem_pa_setup drops it
+        c->fa_ready = false;
+        c->dinv_ready = false;
+        ilu_free(c);
+    }
+    // IntRules.Get(geom, 2p + OrderW + 2) with OrderW = dim - 1 on the multilinear map: order 2p + 3 / 2p + 4,
+    // which MFEM's tensor Gauss-Legendre rules meet with p + 2 / p + 3 points per direction
+    S.rule = make_rule(c->p, nl_tensor_points_1d(c->dim, c->p));
+    S.nq = nq_of(c, S.rule);
 }
 
 // what both setup calls share: the coefficients, the Newton vectors, u_old = 0 and g = 0, an empty history
@@ -87,11 +119,12 @@ void nl_residual(cdfem_ctx *c, const double *u, double *R, double *negR)
 
 // J(u) becomes the assembled operator: the element matrices in k_simplex_elem's layout, then the full
 // assembly's own gather, elimination and SELL fill; what belonged to the previous operator is dropped
-// On quads and hexes nothing is assembled: J(u) becomes the current operator as a copy of u, which the launch
-// points of the linear operator hand to k_nl_tensor (launch_apply_st, launch_diag_elem)
+// On quads and hexes after cdfem_nl_pa_setup nothing is assembled: J(u) becomes the current operator as a copy
+// of u, which the launch points of the linear operator hand to k_nl_tensor (launch_apply_st, launch_diag_elem);
+// after cdfem_nl_fa_setup the element matrices are nl_fa_tensor.hip's and the rest is the simplex sequence
 void nl_jacobian(cdfem_ctx *c, const double *u)
 {
-    if (c->heat.tensor) {
+    if (c->heat.tensor && !c->heat.assembled) {
         NlState &S = c->heat;
         if (u != S.d_ulin.get())
             HIPCHK(hipMemcpyAsync(S.d_ulin, u, c->nl * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -105,9 +138,15 @@ void nl_jacobian(cdfem_ctx *c, const double *u)
         return;
     }
     fa_ensure_pattern(c);
-    HIPCHK(launch_nl_gradient(c, u));
-    HIPCHK(launch_fa_assemble(c));
-    HIPCHK(launch_sell_fill(c));
+    if (c->heat.tensor) {
+        timed(c, CDFEM_K_NL_ASSEMBLE, [&] { HIPCHK(launch_nl_tensor_elem(c, u)); });
+        timed(c, CDFEM_K_FA_GATHER, [&] { HIPCHK(launch_fa_assemble(c)); });
+        timed(c, CDFEM_K_SELL_FILL, [&] { HIPCHK(launch_sell_fill(c)); });
+    } else {
+        HIPCHK(launch_nl_gradient(c, u));
+        HIPCHK(launch_fa_assemble(c));
+        HIPCHK(launch_sell_fill(c));
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->kinds = CDFEM_DIFFUSION | CDFEM_CONVECTION | CDFEM_MASS;
     c->fa_ready = true;
@@ -172,6 +211,7 @@ int cdfem_nl_setup(cdfem_ctx *c, const cdfem_nl_heat_coeffs *k)
         upload(c, S.d_edofs, c->h_dofs);
         nl_init_state(c, k);
         S.tensor = false;
+        S.assembled = false;
         S.ready = true;
         return CDFEM_OK;
     });
@@ -180,31 +220,28 @@ int cdfem_nl_setup(cdfem_ctx *c, const cdfem_nl_heat_coeffs *k)
 int cdfem_nl_pa_setup(cdfem_ctx *c, const cdfem_nl_heat_coeffs *k)
 {
     return guarded(c, [&] {
-        require_mesh(c);
-        if (multi_rank(c)) throw UnsupportedError("the nonlinear heat form runs on one rank");
-        if (c->geom != 0) throw UnsupportedError("simplex meshes take the assembled form: cdfem_nl_setup");
-        if (!nl_tensor_supported(c->dim, c->p))
-            throw UnsupportedError("the matrix-free nonlinear form is built for quads p = 1..3 and hexes p = 1, 2");
-        if (!k) throw ArgError("null coefficients");
-        if (!(k->dt > 0.0)) throw ArgError("dt must be positive");
+        nl_tensor_setup(c, k, "the matrix-free nonlinear form");
         NlState &S = c->heat;
-        S.ready = false;
-        if (S.jac_mf) {  // (a Jacobian of the previous coefficients is no operator any more)
-            S.jac_mf = false;
-            c->dinv_ready = false;
-        }
-        if (c->fa_ready) {  // an assembled linear operator of this mesh is dropped, as cdfem_pa_setup drops it
-            c->fa_ready = false;
-            c->dinv_ready = false;
-            ilu_free(c);
-        }
-        // IntRules.Get(geom, 2p + OrderW + 2) with OrderW = dim - 1 on the multilinear map: order 2p + 3 / 2p + 4,
-        // which MFEM's tensor Gauss-Legendre rules meet with p + 2 / p + 3 points per direction
-        S.rule = make_rule(c->p, nl_tensor_points_1d(c->dim, c->p));
-        S.nq = nq_of(c, S.rule);
         S.d_ulin.alloc(c->nl);
         nl_init_state(c, k);
         S.tensor = true;
+        S.assembled = false;
+        S.ready = true;
+        return CDFEM_OK;
+    });
+}
+
+int cdfem_nl_fa_setup(cdfem_ctx *c, const cdfem_nl_heat_coeffs *k)
+{
+    return guarded(c, [&] {
+        nl_tensor_setup(c, k, "the assembled tensor Jacobian");
+        NlState &S = c->heat;
+        fa_ensure_pattern(c);  // (may refuse: before any state of this setup exists)
+        upload(c, S.d_edofs, c->h_dofs);
+        S.d_jq.alloc(nl_fa_tensor_state_size(c));
+        nl_init_state(c, k);
+        S.tensor = true;
+        S.assembled = true;
         S.ready = true;
         return CDFEM_OK;
     });
@@ -254,6 +291,7 @@ int cdfem_nl_gradient(cdfem_ctx *c, const double *u, int where)
         require_nl(c);
         if (!u) throw ArgError("null vector");
         nl_jacobian(c, dev_in(c, u, where, c->heat.d_u, c->nl));
+        prof_collect(c);
         return CDFEM_OK;
     });
 }
@@ -362,23 +400,62 @@ int cdfem_newton_history(cdfem_ctx *c, double *res, double *upd, int32_t *lin_it
 int cdfem_bdr_set(cdfem_ctx *c, int nbf, const int32_t *face_elem, const int32_t *face_local)
 {
     return guarded(c, [&] {
-        require_simplex_one_rank(c, "the boundary linear form");
+        require_mesh(c);
+        if (multi_rank(c)) throw UnsupportedError("the boundary linear form runs on one rank");
+        const bool tensor = c->geom == 0;
+        if (tensor && !nl_fa_tensor_supported(c->dim, c->p))
+            throw UnsupportedError("the boundary linear form on quad / hex faces is built for quads p = 1..3 and hexes p = 1, 2");
         if (nbf < 0 || (nbf > 0 && (!face_elem || !face_local))) throw ArgError("bad facet list");
-        const int dim = c->dim, p = c->p, nd = c->nd, nfd = facet_ndofs(dim, p);
+        const int dim = c->dim, p = c->p, nd = c->nd, d1 = p + 1;
+        const int nfd = tensor ? (dim == 3 ? d1 * d1 : d1) : facet_ndofs(dim, p);
+        const int nfl = tensor ? 2 * dim : dim + 1;  // local facets of an element
         if ((int64_t)nbf * nfd >= ((int64_t)1 << 31)) throw ArgError("facet E-vector exceeds int32 indexing");
         for (int t = 0; t < nbf; ++t) {
             if (face_elem[t] < 0 || face_elem[t] >= c->ne) throw ArgError("facet element out of range");
-            if (face_local[t] < 0 || face_local[t] > dim) throw ArgError("local facet out of range");
+            if (face_local[t] < 0 || face_local[t] >= nfl) throw ArgError("local facet out of range");
         }
         NlState &S = c->heat;
         S.nbf = 0;
         S.d_b_off.reset();
-        std::vector<double> xi, w;
-        const int nqb = facet_rule(dim, p, xi, w);
-        // facet f's points in the element's reference coordinates (vertex 0 at the origin, vertex k at e_k;
-        // the facet's vertices ascending), and the facet dofs' basis values there
-        std::vector<double> bxi((size_t)(dim + 1) * nqb * dim), btab((size_t)(dim + 1) * nqb * nfd + nqb);
-        for (int f = 0; f <= dim; ++f) {
+        std::vector<double> xi, w, bxi, btab, bverts;
+        int nqb = 0, nqb1 = 0;
+        // quad / hex facet f = 2 axis + side: the axes that remain, ascending
+        const auto rem = [&](int axis, int s) { return s == 0 ? (axis == 0 ? 1 : 0) : (axis == 2 ? 1 : 2); };
+        if (tensor) {
+            // BoundaryLFIntegrator's order p + 1 on segments and squares: MFEM's tensor Gauss-Legendre rule with
+            // (p + 1) / 2 + 1 points per direction, the lower remaining axis fastest
+            nqb1 = (p + 1) / 2 + 1;
+            nqb = dim == 3 ? nqb1 * nqb1 : nqb1;
+            const Rule1D r = make_rule(p, nqb1);
+            btab.resize((size_t)nqb1 * (d1 + 2));
+            for (int q = 0; q < nqb1; ++q) {
+                for (int d = 0; d < d1; ++d) btab[(size_t)q * d1 + d] = r.B[q][d];
+                btab[(size_t)nqb1 * d1 + q] = r.pts[q];
+                btab[(size_t)nqb1 * (d1 + 1) + q] = r.wts[q];
+            }
+            bxi.resize((size_t)nfl * nqb * dim);
+            for (int f = 0; f < nfl; ++f)
+                for (int q = 0; q < nqb; ++q) {
+                    double *x = &bxi[((size_t)f * nqb + q) * dim];
+                    x[f >> 1] = f & 1;
+                    x[rem(f >> 1, 0)] = r.pts[q % nqb1];
+                    if (dim == 3) x[rem(f >> 1, 1)] = r.pts[q / nqb1];
+                }
+            // the facets' element vertices (quads and hexes keep their geometry on the device alone)
+            const size_t nvd = (size_t)c->nv * dim;
+            std::vector<double> verts((size_t)c->ne * nvd);
+            HIPCHK(hipMemcpy(verts.data(), c->d_verts, verts.size() * sizeof(double), hipMemcpyDeviceToHost));
+            bverts.resize((size_t)nbf * nvd);
+            for (int t = 0; t < nbf; ++t)
+                std::copy_n(&verts[(size_t)face_elem[t] * nvd], nvd, &bverts[(size_t)t * nvd]);
+        } else {
+            nqb = facet_rule(dim, p, xi, w);
+            bxi.resize((size_t)(dim + 1) * nqb * dim);
+            btab.resize((size_t)(dim + 1) * nqb * nfd + nqb);
+        }
+        // simplices: facet f's points in the element's reference coordinates (vertex 0 at the origin, vertex k at
+        // e_k; the facet's vertices ascending), and the facet dofs' basis values there
+        for (int f = 0; !tensor && f <= dim; ++f) {
             int v[3], m = 0;
             for (int a = 0; a <= dim; ++a)
                 if (a != f) v[m++] = a;
@@ -394,11 +471,18 @@ int cdfem_bdr_set(cdfem_ctx *c, int nbf, const int32_t *face_elem, const int32_t
                 for (int l = 0; l < nfd; ++l) btab[((size_t)f * nqb + q) * nfd + l] = phi[facet_dof(dim, p, f, l)];
             }
         }
-        for (int q = 0; q < nqb; ++q) btab[(size_t)(dim + 1) * nqb * nfd + q] = w[q];
+        for (int q = 0; !tensor && q < nqb; ++q) btab[(size_t)(dim + 1) * nqb * nfd + q] = w[q];
         // per dof its entries of the facet E-vector [nbf][nfd], ascending facet
         std::vector<int32_t> off(c->nl + 1, 0), pos((size_t)nbf * nfd);
         const auto gdof = [&](int t, int l) {
-            return c->h_dofs[(size_t)face_elem[t] * nd + facet_dof(dim, p, face_local[t], l)];
+            const int f = face_local[t];
+            if (!tensor) return c->h_dofs[(size_t)face_elem[t] * nd + facet_dof(dim, p, f, l)];
+            // the element's lexicographic dofs with axis index 0 or p, the lower remaining axis fastest
+            int idx[3] = {0, 0, 0};
+            idx[f >> 1] = (f & 1) * p;
+            idx[rem(f >> 1, 0)] = l % d1;
+            if (dim == 3) idx[rem(f >> 1, 1)] = l / d1;
+            return c->h_dofs[(size_t)face_elem[t] * nd + idx[0] + d1 * (idx[1] + d1 * idx[2])];
         };
         for (int t = 0; t < nbf; ++t)
             for (int l = 0; l < nfd; ++l) off[gdof(t, l) + 1]++;
@@ -411,6 +495,7 @@ int cdfem_bdr_set(cdfem_ctx *c, int nbf, const int32_t *face_elem, const int32_t
         S.h_face_elem.assign(face_elem, face_elem + nbf);
         S.h_face_local.assign(face_local, face_local + nbf);
         S.h_bxi = bxi;
+        S.h_bverts = bverts;
         upload(c, S.d_face_elem, S.h_face_elem);
         upload(c, S.d_face_local, S.h_face_local);
         upload(c, S.d_btab, btab);
@@ -420,6 +505,7 @@ int cdfem_bdr_set(cdfem_ctx *c, int nbf, const int32_t *face_elem, const int32_t
         upload(c, S.d_b_off, off);
         HIPCHK(hipStreamSynchronize(c->stream));  // the host tables die at scope exit
         S.nqb = nqb;
+        S.nqb1 = nqb1;
         S.nfd = nfd;
         S.nbf = nbf;
         return CDFEM_OK;
@@ -450,7 +536,21 @@ int cdfem_bdr_quadrature_points(cdfem_ctx *c, double *xyz, int where)
         const NlState &S = c->heat;
         const int dim = c->dim, nv = dim + 1, nqb = S.nqb;
         std::vector<double> out((size_t)S.nbf * nqb * dim);
-        for (int t = 0; t < S.nbf; ++t) {  // affine simplices: x = v0 + J xi, evaluated on the host
+        for (int t = 0; c->geom == 0 && t < S.nbf; ++t) {  // quads / hexes: the multilinear map, on the host
+            const double *V = &S.h_bverts[(size_t)t * c->nv * dim];
+            const double *X = &S.h_bxi[(size_t)S.h_face_local[t] * nqb * dim];
+            for (int q = 0; q < nqb; ++q)
+                for (int k = 0; k < dim; ++k) {
+                    double x = 0.0;
+                    for (int v = 0; v < c->nv; ++v) {
+                        double N = 1.0;
+                        for (int m = 0; m < dim; ++m) N *= ((v >> m) & 1) ? X[(size_t)q * dim + m] : 1.0 - X[(size_t)q * dim + m];
+                        x += N * V[v * dim + k];
+                    }
+                    out[((size_t)t * nqb + q) * dim + k] = x;
+                }
+        }
+        for (int t = 0; c->geom != 0 && t < S.nbf; ++t) {  // affine simplices: x = v0 + J xi, evaluated on the host
             const double *V = &c->h_verts[(size_t)S.h_face_elem[t] * nv * dim];
             const double *X = &S.h_bxi[(size_t)S.h_face_local[t] * nqb * dim];
             for (int q = 0; q < nqb; ++q)

@@ -14,6 +14,7 @@
 //                 eliminated matrix and the SELL copy of the full assembly run unchanged;
 // k_bdr_lf        one thread per boundary facet: the facet's dofs from facet_dof's table over the element's local
 //                 dof order, the facet E-vector summed per dof in ascending facet order (k_bdr_gather).
+//                 (Quad / hex faces: k_bdr_lf_tensor of nl_fa_tensor.hip, the same gather.)
 // No atomics: every sum has one fixed order.
 #include <hip/hip_runtime.h>
 
@@ -314,7 +315,7 @@ hipError_t launch_bdr_lf(cdfem_ctx *c, const double *gq, double *b)
 {
     if (c->heat.nbf > 0) {
         const dim3 g((c->heat.nbf + 63) / 64), blk(64);
-        const hipError_t e = dispatch_simplex(c, [&](auto D, auto P) {
+        const hipError_t e = c->geom == 0 ? launch_bdr_lf_tensor(c, gq) : dispatch_simplex(c, [&](auto D, auto P) {
             hipLaunchKernelGGL((k_bdr_lf<D(), P()>), g, blk, 0, c->stream, c->d_verts.get(), c->heat.d_face_elem.get(),
                                c->heat.d_face_local.get(), c->heat.nbf, c->heat.nqb, c->heat.d_btab.get(), gq,
                                c->heat.d_bYe.get());

@@ -34,6 +34,7 @@ RULE_OPERATOR, RULE_LINEARFORM, RULE_ERROR, RULE_DIFFUSION, RULE_CONVECTION, RUL
 RULE_NONLINEAR = 6
 K_APPLY, K_E2L, K_UPDATE, K_DIRECTION, K_ORTH = 0, 1, 2, 3, 4
 K_NL_RESIDUAL, K_DIAGONAL = 5, 6
+K_NL_ASSEMBLE, K_FA_GATHER, K_SELL_FILL = 7, 8, 9
 
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_NOT_CONVERGED, ERR_COMM = range(7)
 
@@ -165,6 +166,7 @@ def _declare(L):
         "cdfem_gmsh_mesh": (C.c_int, [C.c_char_p, C.c_int, _dp, _ip, _ip, _dp]),
         "cdfem_nl_setup": (C.c_int, [vp, C.POINTER(NlHeatCoeffs)]),
         "cdfem_nl_pa_setup": (C.c_int, [vp, C.POINTER(NlHeatCoeffs)]),
+        "cdfem_nl_fa_setup": (C.c_int, [vp, C.POINTER(NlHeatCoeffs)]),
         "cdfem_nl_set_old": (C.c_int, [vp, vp, C.c_int]),
         "cdfem_nl_set_rhs": (C.c_int, [vp, vp, C.c_int]),
         "cdfem_nl_residual": (C.c_int, [vp, vp, vp, C.c_int]),
@@ -625,7 +627,7 @@ class Context:
         return X, dict(converged=bool(res.converged), iterations=res.iterations,
                        final_norm=res.final_norm, initial_norm=res.initial_norm, seconds=res.seconds)
 
-    # -- nonlinear heat form, Newton, boundary linear form (simplex meshes) --------------------------
+    # -- nonlinear heat form, Newton, boundary linear form -------------------------------------------
     def nl_setup(self, dt, a0, a1, m0, m1, u_ref=0.0):
         """Backward-Euler quasi-linear heat form: a(u) = a0 + a1 (u - u_ref), m(u) = m0 + m1 (u - u_ref)."""
         k = NlHeatCoeffs(float(dt), float(a0), float(a1), float(m0), float(m1), float(u_ref))
@@ -637,6 +639,14 @@ class Context:
         of mult, diagonal and solve, and the other nl_* / newton_solve* methods work as on simplices."""
         k = NlHeatCoeffs(float(dt), float(a0), float(a1), float(m0), float(m1), float(u_ref))
         self._chk(self.L.cdfem_nl_pa_setup(self.h, C.byref(k)))
+        return self
+
+    def nl_fa_setup(self, dt, a0, a1, m0, m1, u_ref=0.0):
+        """The same form on a quad / hex mesh with the Jacobian assembled: nl_gradient(u), and every rebuild of
+        newton_solve*, assembles J(u) into the full assembly's CSR, so fa_csr() exports it and solve takes
+        pc="ilu".  The assembled J is a snapshot: a later nl_set_old leaves it until the next nl_gradient."""
+        k = NlHeatCoeffs(float(dt), float(a0), float(a1), float(m0), float(m1), float(u_ref))
+        self._chk(self.L.cdfem_nl_fa_setup(self.h, C.byref(k)))
         return self
 
     def nl_set_old(self, u_old, where=HOST):
@@ -714,7 +724,8 @@ class Context:
         return info, hist
 
     def bdr_set(self, elem, local_face):
-        """The boundary facets of the boundary linear form (boundary_facets(mesh, select))."""
+        """The boundary facets of the boundary linear form: (element, local facet) pairs, on simplices from
+        boundary_facets(mesh, select); on quad / hex meshes local facet = 2 * axis + side."""
         e, f = _i32(elem), _i32(local_face)
         if len(e) != len(f):
             raise ValueError("elem and local_face differ in length")

@@ -57,12 +57,15 @@ enum { CDFEM_PC_NONE = 0, CDFEM_PC_JACOBI = 1, CDFEM_PC_ILU = 2 };
  * MFEM's tabulated rules: DIFFUSION order 2p - 2, CONVECTION and MASS order 2p (OPERATOR refused). */
 enum { CDFEM_RULE_OPERATOR = 0, CDFEM_RULE_LINEARFORM = 1, CDFEM_RULE_ERROR = 2, CDFEM_RULE_DIFFUSION = 3,
        CDFEM_RULE_CONVECTION = 4, CDFEM_RULE_MASS = 5,
-       CDFEM_RULE_NONLINEAR = 6 /* after cdfem_nl_setup / cdfem_nl_pa_setup: the nonlinear heat form's rule */ };
+       CDFEM_RULE_NONLINEAR = 6 /* after cdfem_nl_setup / cdfem_nl_pa_setup / cdfem_nl_fa_setup: the heat form's */ };
 /* kernel ids for cdfem_profile_read */
 enum { CDFEM_K_APPLY = 0, CDFEM_K_E2L = 1, CDFEM_K_UPDATE = 2, CDFEM_K_DIRECTION = 3, CDFEM_K_ORTH = 4,
        CDFEM_K_NL_RESIDUAL = 5, CDFEM_K_DIAGONAL = 6, /* profiling slots: cdfem_nl_pa_setup's residual kernel;
                                                           the element part of cdfem_pa_diagonal */
-       CDFEM_K_COUNT = 8 };
+       /* one Jacobian rebuild after cdfem_nl_fa_setup, in its three parts: the element matrices (point state and
+        * rows), the gather with the elimination, the SELL fill */
+       CDFEM_K_NL_ASSEMBLE = 7, CDFEM_K_FA_GATHER = 8, CDFEM_K_SELL_FILL = 9,
+       CDFEM_K_COUNT = 10 };
 
 int cdfem_abi_version(void);
 
@@ -162,10 +165,10 @@ int cdfem_pa_setup_form(cdfem_ctx *ctx, const cdfem_form_coeffs *form);
  * CDFEM_RULE_OPERATOR rule there (Gauss-Legendre, p + 1 points per direction on quads, p + 2 on hexes), and
  * every per-point array (kappa_q, kappa_mat_q, conv_q, mass_q) is sampled at its points, in the order
  * cdfem_quadrature_points(CDFEM_RULE_OPERATOR) returns, as for cdfem_pa_setup.  The assembled operator replaces
- * a partial-assembly one on the same context and the other way round (a later cdfem_pa_setup or
- * cdfem_nl_pa_setup drops it, with its Jacobi scale and ILU(0) factors; the pattern is kept for the next
- * cdfem_fa_setup).  On a context declared structured the solves then run the SpMV, not the brick kernels, and
- * CDFEM_PC_ILU becomes available to GMRES and BiCGStab as on simplices.                                   */
+ * a partial-assembly one on the same context and the other way round (a later cdfem_pa_setup,
+ * cdfem_nl_pa_setup or cdfem_nl_fa_setup drops it, with its Jacobi scale and ILU(0) factors; the pattern is kept
+ * for the next cdfem_fa_setup).  On a context declared structured the solves then run the SpMV, not the brick
+ * kernels, and CDFEM_PC_ILU becomes available to GMRES and BiCGStab as on simplices.                      */
 int cdfem_mesh_upload_simplex(cdfem_ctx *ctx, int dim, int order, int ne, const double *elem_verts,
                               int64_t nldofs, const int32_t *elem_dofs, int n_ess, const int32_t *ess_dofs);
 int cdfem_fa_setup(cdfem_ctx *ctx, unsigned kinds, double kappa, const double *kappa_q, double alpha,
@@ -278,7 +281,7 @@ int cdfem_nl_gradient(cdfem_ctx *ctx, const double *u, int where);
  * one more than the operator rule.  (Derived from MFEM's sources, not pinned against an MFEM run: DESIGN 2.)
  * CDFEM_RULE_NONLINEAR reports it: (p + 2)^2 / (p + 3)^3 points, q lexicographic with qx fastest.
  * Afterwards cdfem_nl_set_old, cdfem_nl_set_rhs, cdfem_nl_residual, cdfem_newton_solve and
- * cdfem_newton_history behave as on simplices (g any L-vector; cdfem_bdr_* stays simplex-only).
+ * cdfem_newton_history behave as on simplices (g any L-vector, cdfem_bdr_lf_assemble's among them).
  * cdfem_nl_gradient assembles nothing: it keeps a copy of u and makes J(u) the context's current operator, on
  * which cdfem_pa_mult (constrained 0 / 1 / 2), cdfem_pa_diagonal and cdfem_solve (CG, GMRES, BiCGStab; no
  * preconditioner or Jacobi; CDFEM_PC_ILU needs an assembled operator) act matrix-free, the constrained forms on
@@ -286,6 +289,24 @@ int cdfem_nl_gradient(cdfem_ctx *ctx, const double *u, int where);
  * no structured fast path runs and cdfem_kernel_name(CDFEM_K_APPLY) is "k_nl_tensor"; a later cdfem_pa_setup
  * makes the linear operator current again.                                                             */
 int cdfem_nl_pa_setup(cdfem_ctx *ctx, const cdfem_nl_heat_coeffs *coeffs);
+
+/* quad / hex meshes, one rank: the same form, rule (CDFEM_RULE_NONLINEAR) and refusals as cdfem_nl_pa_setup, with
+ * the Jacobian assembled: what Input/petsc_nonlinear.opts asks for (GMRES with bjacobi / ilu on every Newton step).
+ * cdfem_nl_set_old, cdfem_nl_set_rhs, cdfem_nl_residual (the matrix-free kernel), cdfem_newton_solve and
+ * cdfem_newton_history are unchanged.  cdfem_nl_gradient(u), and every Jacobian rebuild of cdfem_newton_solve,
+ * assembles J(u) on the GPU into the full assembly's CSR of this mesh (cdfem_fa_setup's pattern, gather,
+ * elimination and SELL copy; the element matrices are the formula above on the multilinear map).  Afterwards
+ * cdfem_pa_mult (constrained 0 / 1 / 2), cdfem_pa_diagonal, cdfem_fa_csr and cdfem_solve act on the assembled
+ * matrix, the constrained forms on the eliminated one; cdfem_solve takes CG, GMRES and BiCGStab with no
+ * preconditioner, Jacobi or CDFEM_PC_ILU, and cdfem_kernel_name(CDFEM_K_APPLY) names the SpMV.
+ * The assembled J is a snapshot of u and of the u_old set when it was assembled: a later cdfem_nl_set_old does
+ * not change it until the next cdfem_nl_gradient (the matrix-free J of cdfem_nl_pa_setup reads the current
+ * u_old).  Whichever of cdfem_nl_pa_setup and cdfem_nl_fa_setup was called last owns the nonlinear state; each
+ * drops the other's Jacobian and an assembled linear operator.  cdfem_pa_setup, cdfem_fa_setup and
+ * cdfem_nl_pa_setup called afterwards drop the assembled Jacobian as they drop an assembled linear operator; the
+ * pattern is kept.  cdfem_profile_read(CDFEM_K_NL_ASSEMBLE / CDFEM_K_FA_GATHER / CDFEM_K_SELL_FILL) time the
+ * three parts of a rebuild.                                                                             */
+int cdfem_nl_fa_setup(cdfem_ctx *ctx, const cdfem_nl_heat_coeffs *coeffs);
 
 /* replaces: NewtonPetscSolver::Solve (newton_petsc_solver.hpp:180-259; Input/petsc_nonlinear.opts for the
  * linear solve).  For iter = 0 .. max_iter - 1: R = residual(u), rn = ||R||_2; r0 = max(1, rn) on iteration 0;
@@ -313,7 +334,7 @@ int cdfem_newton_solve(cdfem_ctx *ctx, const cdfem_newton_params *prm, const cdf
                        double *u, int where, cdfem_newton_result *res);
 int cdfem_newton_history(cdfem_ctx *ctx, double *res, double *upd, int32_t *lin_its, int cap, int *count);
 
-/* ---- boundary linear form (simplex meshes) --------------------------------------------------------
+/* ---- boundary linear form (one rank) ---------------------------------------------------------------
  * replaces: neumann_form.AddBoundaryIntegrator(new BoundaryLFIntegrator(flux_coeff), x_bdr); Assemble()
  * (nonlinear_convection_diffusion_1D.cpp:830-831, :952-954).  cdfem_bdr_set: the nbf boundary facets as (element,
  * local facet f = the facet opposite local vertex f); the facet's vertices are the element's other vertices in
@@ -322,7 +343,16 @@ int cdfem_newton_history(cdfem_ctx *ctx, double *res, double *upd, int32_t *lin_
  * segments Gauss-Legendre with (p + 1) / 2 + 1 points, triangular facets MFEM's tabulated rule of order p + 1.
  * cdfem_bdr_quadrature_points: nbf * nq * dim physical coordinates, facet-major.
  * cdfem_bdr_lf_assemble: b_i = sum_q w_q (edge length | |t1 x t2|) g_q phi_i(q), g_q the nbf * nq point
- * values; b is an L-vector (what cdfem_nl_set_rhs takes).                                              */
+ * values; b is an L-vector (what cdfem_nl_set_rhs takes).
+ * Quad and hex meshes (quads p = 1..3, hexes p = 1, 2; cdfem_bdr_set needs only the mesh): the local facet is
+ * f = 2 axis + side, side 0 at xi_axis = 0 and side 1 at xi_axis = 1 in the lexicographic vertex / dof convention
+ * of cdfem_mesh_upload; f outside 0 .. 2 dim - 1 is CDFEM_ERR_ARG.  The facet's (p + 1)^(dim - 1) dofs are the
+ * element's local dofs whose axis index is 0 or p, the lower remaining axis fastest.  The rule is the same default
+ * order p + 1, which MFEM's segment and square rules meet with tensor Gauss-Legendre of n = (p + 1) / 2 + 1 points
+ * per direction (derived from MFEM's sources, as the simplex rule was; not pinned against an MFEM run):
+ * cdfem_bdr_rule_size gives n^(dim - 1), the lower remaining axis fastest.  cdfem_bdr_quadrature_points returns
+ * the image under the element's multilinear map, which is not affine.  cdfem_bdr_lf_assemble uses the edge length
+ * in 2D and |dx/ds x dx/dt| at the point in 3D (a perturbed hex face is bilinear).                        */
 int cdfem_bdr_set(cdfem_ctx *ctx, int nbf, const int32_t *face_elem, const int32_t *face_local);
 int cdfem_bdr_rule_size(cdfem_ctx *ctx, int *nq_per_facet);
 int cdfem_bdr_quadrature_points(cdfem_ctx *ctx, double *xyz, int where);
