@@ -586,16 +586,28 @@ hipError_t launch_nl_gradient(cdfem_ctx *c, const double *u);
 hipError_t launch_nl_finish(cdfem_ctx *c, double *R, const double *g, double *negR);
 // facet E-vector from the point values gq, then b = its per-dof sums in ascending facet order
 hipError_t launch_bdr_lf(cdfem_ctx *c, const double *gq, double *b);
-// the same form on quads and hexes, matrix-free (nl_tensor.hip): the spaces it is built for, its rule's points
-// per direction, and k_nl_tensor in mode 0 (Ye = the elements' shares of R(u)), 1 (of J(u) v; con: essential
-// entries of v read as 0) or 2 (of J(u)'s diagonal), Ye in the context's E-vector layout; u_old from c->heat
+inline cdfem_nl_heat_coeffs nl_coeffs(const cdfem_ctx *c)
+{
+    return cdfem_nl_heat_coeffs{c->heat.dt, c->heat.a0, c->heat.a1, c->heat.m0, c->heat.m1, c->heat.u_ref};
+}
+// the same form on quads and hexes (nl_tensor.hip, nl_fa_tensor.hip, the boundary form's faces): the spaces it is
+// built for (quads of p = 1..3, hexes of p = 1, 2), f(DIM, P) as constants for them, and its rule's points per
+// direction
 bool nl_tensor_supported(int dim, int p);
-int nl_tensor_points_1d(int dim, int p);
+template <class F>
+hipError_t dispatch_nl_tensor(const cdfem_ctx *c, F &&f)
+{
+    return dispatch_value<21, 22, 23, 31, 32>(10 * c->dim + c->p, hipErrorInvalidValue, [&](auto DP) {
+        return f(std::integral_constant<int, DP() / 10>{}, std::integral_constant<int, DP() % 10>{});
+    });
+}
+__host__ __device__ constexpr int nl_tensor_points_1d(int dim, int p) { return dim == 3 ? p + 3 : p + 2; }
+// matrix-free: k_nl_tensor in mode 0 (Ye = the elements' shares of R(u)), 1 (of J(u) v; con: essential entries of
+// v read as 0) or 2 (of J(u)'s diagonal), Ye in the context's E-vector layout; u_old from c->heat
 hipError_t launch_nl_tensor(cdfem_ctx *c, int mode, const double *u, const double *v, bool con, double *Ye,
                             const KrylovState *st);
-// the same form with the Jacobian assembled (nl_fa_tensor.hip): the spaces it is built for, the doubles of the
-// point state c->heat.d_jq, and d_Ee = the element matrices of J(u) (k_nl_tensor_point, then k_nl_tensor_elem)
-bool nl_fa_tensor_supported(int dim, int p);
+// with the Jacobian assembled (nl_fa_tensor.hip): the doubles of the point state c->heat.d_jq, and d_Ee = the
+// element matrices of J(u) (k_nl_tensor_point, then k_nl_tensor_elem)
 size_t nl_fa_tensor_state_size(const cdfem_ctx *c);
 hipError_t launch_nl_tensor_elem(cdfem_ctx *c, const double *u);
 // the facet E-vector of the boundary linear form on quad / hex faces (k_bdr_lf_tensor; launch_bdr_lf gathers it)

@@ -25,6 +25,7 @@
 
 #include "cdfem_internal.hpp"
 #include "dispatch.hpp"
+#include "point_geom.hpp"
 #include "reduce.hpp"
 
 namespace cdfem {
@@ -181,31 +182,8 @@ k_simplex_elem(const double *__restrict__ verts, int ne, int nqd, int nqc, const
     constexpr int ND = P == 1 ? DIM + 1 : P == 2 ? (DIM + 1) * (DIM + 2) / 2 : 10;
     const int e = blockIdx.x * 64 + threadIdx.x;
     if (e >= ne) return;
-    const double *V = verts + (size_t)e * (DIM + 1) * DIM;
-    double J[DIM][DIM], A[DIM][DIM];
-#pragma unroll
-    for (int k = 0; k < DIM; ++k)
-#pragma unroll
-        for (int m = 0; m < DIM; ++m) J[k][m] = V[(m + 1) * DIM + k] - V[k];
-    double det;
-    if constexpr (DIM == 3) {
-        A[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-        A[0][1] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
-        A[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
-        A[1][0] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-        A[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
-        A[1][2] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
-        A[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-        A[2][1] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
-        A[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-        det = J[0][0] * A[0][0] + J[0][1] * A[1][0] + J[0][2] * A[2][0];
-    } else {
-        A[0][0] = J[1][1];
-        A[0][1] = -J[0][1];
-        A[1][0] = -J[1][0];
-        A[1][1] = J[0][0];
-        det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-    }
+    double A[DIM][DIM];
+    const double det = simplex_adjugate<DIM>(verts + (size_t)e * (DIM + 1) * DIM, A);
     double M[ND][ND];
 #pragma unroll
     for (int i = 0; i < ND; ++i)
@@ -316,17 +294,8 @@ k_simplex_lf(const double *__restrict__ verts, int ne, int nq, const double *__r
 {
     const int e = blockIdx.x * 64 + threadIdx.x;
     if (e >= ne) return;
-    const double *V = verts + (size_t)e * (DIM + 1) * DIM;
-    double det;
-    if constexpr (DIM == 3) {
-        double J[3][3];
-        for (int k = 0; k < 3; ++k)
-            for (int m = 0; m < 3; ++m) J[k][m] = V[(m + 1) * 3 + k] - V[k];
-        det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
-              J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-    } else {
-        det = (V[2] - V[0]) * (V[5] - V[1]) - (V[4] - V[0]) * (V[3] - V[1]);
-    }
+    double A[DIM][DIM];  // (unused: the load needs det J only)
+    const double det = simplex_adjugate<DIM>(verts + (size_t)e * (DIM + 1) * DIM, A);
     double b[ND];
 #pragma unroll
     for (int l = 0; l < ND; ++l) b[l] = 0.0;

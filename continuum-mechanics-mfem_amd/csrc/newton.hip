@@ -64,7 +64,7 @@ void nl_tensor_setup(cdfem_ctx *c, const cdfem_nl_heat_coeffs *k, const char *wh
     require_mesh(c);
     if (multi_rank(c)) throw UnsupportedError("the nonlinear heat form runs on one rank");
     if (c->geom != 0) throw UnsupportedError("simplex meshes take the assembled form: cdfem_nl_setup");
-    if (!nl_tensor_supported(c->dim, c->p) || !nl_fa_tensor_supported(c->dim, c->p))
+    if (!nl_tensor_supported(c->dim, c->p))
         throw UnsupportedError(std::string(what) + " is built for quads p = 1..3 and hexes p = 1, 2");
     if (!k) throw ArgError("null coefficients");
     if (!(k->dt > 0.0)) throw ArgError("dt must be positive");
@@ -403,7 +403,7 @@ int cdfem_bdr_set(cdfem_ctx *c, int nbf, const int32_t *face_elem, const int32_t
         require_mesh(c);
         if (multi_rank(c)) throw UnsupportedError("the boundary linear form runs on one rank");
         const bool tensor = c->geom == 0;
-        if (tensor && !nl_fa_tensor_supported(c->dim, c->p))
+        if (tensor && !nl_tensor_supported(c->dim, c->p))
             throw UnsupportedError("the boundary linear form on quad / hex faces is built for quads p = 1..3 and hexes p = 1, 2");
         if (nbf < 0 || (nbf > 0 && (!face_elem || !face_local))) throw ArgError("bad facet list");
         const int dim = c->dim, p = c->p, nd = c->nd, d1 = p + 1;

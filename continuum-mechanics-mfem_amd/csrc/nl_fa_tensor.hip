@@ -15,10 +15,10 @@
 //                      2 + dim doubles into d_jq[e / 64][q][2 + dim][e % 64].  u - u_old is interpolated from the
 //                      per-dof differences and the gradient is taken of u - u(dof 0), as k_nl_tensor does
 //                      (nl_kernels.hip nl_point says why).
-//   k_nl_tensor_elem   k_tensor_elem's mapping: a wave is the 64 elements of one Ee block (lane = e % 64) times
-//                      one row i (blockIdx.y); with t = s A A^T g_i the row update is
-//                        acc[j] += w . g_j + m phi_j,   w = a(u) t,   m = W det mu phi_i + a1 (t . g_u),
-//                      the point state read in 512-byte wave loads, the nd stores 512 contiguous bytes each.
+//   k_nl_tensor_elem   the row core of point_geom.hpp (tensor_elem_row, as k_tensor_elem) with this form's point
+//                      functor: with t = s A A^T g_i,
+//                        w = a(u) t,   m = W det mu phi_i + a1 (t . g_u),
+//                      the point state read in 512-byte wave loads.
 // The point state is formed once and read by all nd rows: forming it in the row kernel would cost every row the
 // nd-term interpolations again and hold the element's 2 nd dof values next to the nd accumulators.
 // No LDS, no atomics, no scratch, one fixed summation order.
@@ -31,69 +31,14 @@
 #include <hip/hip_runtime.h>
 
 #include "cdfem_internal.hpp"
-#include "dispatch.hpp"
+#include "point_geom.hpp"
 
 namespace cdfem {
 
 namespace {
 
-// J[i][k] = d x_i / d xi_k of the multilinear map (lexicographic vertices: bit k of the vertex number is its
-// position along axis k)
-template <int DIM>
-__device__ __forceinline__ void nlfa_jacobian(const double (&V)[(1 << DIM) * DIM], const double (&xi)[DIM], double (&J)[DIM][DIM])
-{
-#pragma unroll
-    for (int i = 0; i < DIM; ++i)
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) J[i][k] = 0.0;
-#pragma unroll
-    for (int v = 0; v < (1 << DIM); ++v) {
-        double f[DIM];
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) f[k] = ((v >> k) & 1) ? xi[k] : 1.0 - xi[k];
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) {
-            double dN = ((v >> k) & 1) ? 1.0 : -1.0;
-#pragma unroll
-            for (int m = 0; m < DIM; ++m)
-                if (m != k) dN *= f[m];
-#pragma unroll
-            for (int i = 0; i < DIM; ++i) J[i][k] += V[v * DIM + i] * dN;
-        }
-    }
-}
-
-// adj(J) (A[a][k] = det J d xi_a / d x_k) and det J
-template <int DIM>
-__device__ __forceinline__ double nlfa_adjugate(const double (&J)[DIM][DIM], double (&A)[DIM][DIM])
-{
-    if constexpr (DIM == 2) {
-        A[0][0] = J[1][1]; A[0][1] = -J[0][1];
-        A[1][0] = -J[1][0]; A[1][1] = J[0][0];
-        return J[0][0] * J[1][1] - J[0][1] * J[1][0];
-    } else {
-        A[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-        A[0][1] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
-        A[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
-        A[1][0] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-        A[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
-        A[1][2] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
-        A[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-        A[2][1] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
-        A[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-        return J[0][0] * A[0][0] + J[0][1] * A[1][0] + J[0][2] * A[2][0];
-    }
-}
-
 template <int DIM, int P>
-struct NlFaShape {
-    static constexpr int D1 = P + 1;
-    static constexpr int Q1 = DIM == 3 ? P + 3 : P + 2;
-    static constexpr int DZ = DIM == 3 ? D1 : 1;
-    static constexpr int QZ = DIM == 3 ? Q1 : 1;
-    static constexpr int ND = D1 * D1 * DZ;
-    static constexpr int NQ = Q1 * Q1 * QZ;
-    static constexpr int NV = 1 << DIM;
+struct NlFaShape : TensorShape<DIM, P, nl_tensor_points_1d(DIM, P)> {
     static constexpr int NC = 2 + DIM;  // a(u), mu, the reference gradient of u
 };
 
@@ -148,88 +93,26 @@ k_nl_tensor_elem(const double *__restrict__ verts, int ne, const Rule1D r, doubl
                  double *__restrict__ Ee)
 {
     using S = NlFaShape<DIM, P>;
-    constexpr int D1 = S::D1, Q1 = S::Q1, DZ = S::DZ, ND = S::ND, NQ = S::NQ, NV = S::NV, NC = S::NC;
-    const int e = blockIdx.x * kLanes + threadIdx.x;
-    const int i = blockIdx.y;  // the row: wave-uniform
-    if (e >= ne) return;       // (padding lanes of the last block: their entries are never gathered)
-    const int ix = i % D1, iy = (i / D1) % D1, iz = i / (D1 * D1);
-    double V[NV * DIM];
-#pragma unroll
-    for (int n = 0; n < NV * DIM; ++n) V[n] = verts[(size_t)e * NV * DIM + n];
-    double acc[ND];
-#pragma unroll
-    for (int j = 0; j < ND; ++j) acc[j] = 0.0;
+    constexpr int NQ = S::NQ, NC = S::NC;
     const double *pq = jq + (size_t)blockIdx.x * NQ * NC * kLanes + threadIdx.x;
-#pragma unroll 1
-    for (int q = 0; q < NQ; ++q) {
-        const int qx = q % Q1, qy = (q / Q1) % Q1, qz = q / (Q1 * Q1);
-        double xi[DIM], W = r.wts[qx] * r.wts[qy];
-        xi[0] = r.pts[qx];
-        xi[1] = r.pts[qy];
-        if constexpr (DIM == 3) {
-            xi[2] = r.pts[qz];
-            W *= r.wts[qz];
-        }
-        double J[DIM][DIM], A[DIM][DIM];
-        nlfa_jacobian<DIM>(V, xi, J);
-        const double det = nlfa_adjugate<DIM>(J, A);
+    tensor_elem_row<DIM, P, S::Q1>(verts, ne, r, [&](int, int q, double W, double det, const double (&A)[DIM][DIM],
+                                                     double phi, const double (&gi)[DIM], double (&w)[DIM], double &m) {
         // the point state
         const double *sq = pq + (size_t)q * NC * kLanes;
         const double au = sq[0], mu = sq[kLanes];
         double gu[DIM];
 #pragma unroll
         for (int a = 0; a < DIM; ++a) gu[a] = sq[(size_t)(2 + a) * kLanes];
-        // the row's basis function at the point: value and reference gradient
-        const double bx = r.B[qx][ix], gx = r.G[qx][ix], by = r.B[qy][iy], gy = r.G[qy][iy];
-        const double bz = DIM == 3 ? r.B[qz][iz] : 1.0, gz = DIM == 3 ? r.G[qz][iz] : 0.0;
-        const double phi = bx * by * bz;
-        double gi[DIM];
-        gi[0] = gx * by * bz;
-        gi[1] = bx * gy * bz;
-        if constexpr (DIM == 3) gi[2] = bx * by * gz;
         // t = s A A^T g_i
-        double gk[DIM], t[DIM];
+        double t[DIM], tg = 0.0;
+        metric_flux<DIM>(A, W / det, gi, t);
 #pragma unroll
-        for (int n = 0; n < DIM; ++n) {
-            gk[n] = 0.0;
-#pragma unroll
-            for (int a = 0; a < DIM; ++a) gk[n] += A[a][n] * gi[a];
-        }
-        const double s = W / det;
-        double tg = 0.0;
-#pragma unroll
-        for (int b = 0; b < DIM; ++b) {
-            double v = 0.0;
-#pragma unroll
-            for (int n = 0; n < DIM; ++n) v += A[b][n] * gk[n];
-            t[b] = s * v;
-            tg += t[b] * gu[b];
-        }
-        double w[DIM];
+        for (int b = 0; b < DIM; ++b) tg += t[b] * gu[b];
 #pragma unroll
         for (int b = 0; b < DIM; ++b) w[b] = au * t[b];
-        const double m = (W * det) * mu * phi + a1 * tg;
-        // the row: acc[j] += w . g_j + m phi_j, the y and z factors of column j shared along x
-#pragma unroll
-        for (int jz = 0; jz < DZ; ++jz)
-#pragma unroll
-            for (int jy = 0; jy < D1; ++jy) {
-                const double Bz = DIM == 3 ? r.B[qz][jz] : 1.0, Gz = DIM == 3 ? r.G[qz][jz] : 0.0;
-                const double byz = r.B[qy][jy] * Bz;
-                const double t0 = w[0] * byz;  // times G_x
-                double t1 = w[1] * (r.G[qy][jy] * Bz) + m * byz;  // times B_x
-                if constexpr (DIM == 3) t1 += w[2] * (r.B[qy][jy] * Gz);
-#pragma unroll
-                for (int jx = 0; jx < D1; ++jx) acc[jx + D1 * (jy + D1 * jz)] += r.G[qx][jx] * t0 + r.B[qx][jx] * t1;
-            }
-    }
-    // Ee[((e / 64) nd^2 + i nd + j) 64 + e % 64]: each j one 512-byte wave store
-    double *out = Ee + ((size_t)blockIdx.x * ND * ND + (size_t)i * ND) * kLanes + threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < ND; ++j) out[(size_t)j * kLanes] = acc[j];
+        m = (W * det) * mu * phi + a1 * tg;
+    }, Ee);
 }
-
-bool nl_fa_tensor_supported(int dim, int p) { return dim == 2 ? (p >= 1 && p <= 3) : (dim == 3 && (p == 1 || p == 2)); }
 
 size_t nl_fa_tensor_state_size(const cdfem_ctx *c)
 {
@@ -239,15 +122,13 @@ size_t nl_fa_tensor_state_size(const cdfem_ctx *c)
 // d_Ee = the element matrices of J(u); u_old, the rule and the coefficients from c->heat
 hipError_t launch_nl_tensor_elem(cdfem_ctx *c, const double *u)
 {
-    if (!nl_fa_tensor_supported(c->dim, c->p)) return hipErrorInvalidValue;
     const NlState &H = c->heat;
-    if (H.rule.q1 != (c->dim == 3 ? c->p + 3 : c->p + 2) || !H.d_jq || !H.d_edofs || !c->d_Ee) return hipErrorInvalidValue;
-    const cdfem_nl_heat_coeffs k{H.dt, H.a0, H.a1, H.m0, H.m1, H.u_ref};
+    if (H.rule.q1 != nl_tensor_points_1d(c->dim, c->p) || !H.d_jq || !H.d_edofs || !c->d_Ee) return hipErrorInvalidValue;
     const unsigned nb = (unsigned)((c->ne + kLanes - 1) / kLanes);
-    return dispatch_value<21, 22, 23, 31, 32>(10 * c->dim + c->p, hipErrorInvalidValue, [&](auto DP) {
-        constexpr int DIM = DP() / 10, P = DP() % 10;
+    return dispatch_nl_tensor(c, [&](auto D, auto Pc) {
+        constexpr int DIM = D(), P = Pc();
         hipLaunchKernelGGL((k_nl_tensor_point<DIM, P>), dim3(nb, NlFaShape<DIM, P>::NQ), dim3(kLanes), 0, c->stream,
-                           H.d_edofs.get(), c->ne, H.rule, k, u, H.d_uold.get(), H.d_jq.get());
+                           H.d_edofs.get(), c->ne, H.rule, nl_coeffs(c), u, H.d_uold.get(), H.d_jq.get());
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((k_nl_tensor_elem<DIM, P>), dim3(nb, NlFaShape<DIM, P>::ND), dim3(kLanes), 0, c->stream,
@@ -320,8 +201,8 @@ k_bdr_lf_tensor(const double *__restrict__ verts, const int32_t *__restrict__ fa
 hipError_t launch_bdr_lf_tensor(cdfem_ctx *c, const double *gq)
 {
     const NlState &H = c->heat;
-    return dispatch_value<21, 22, 23, 31, 32>(10 * c->dim + c->p, hipErrorInvalidValue, [&](auto DP) {
-        hipLaunchKernelGGL((k_bdr_lf_tensor<DP() / 10, DP() % 10>), dim3((unsigned)((H.nbf + kLanes - 1) / kLanes)),
+    return dispatch_nl_tensor(c, [&](auto D, auto P) {
+        hipLaunchKernelGGL((k_bdr_lf_tensor<D(), P()>), dim3((unsigned)((H.nbf + kLanes - 1) / kLanes)),
                            dim3(kLanes), 0, c->stream, c->d_verts.get(), H.d_face_elem.get(), H.d_face_local.get(),
                            H.nbf, H.nqb1, H.d_btab.get(), gq, H.d_bYe.get());
         return hipGetLastError();

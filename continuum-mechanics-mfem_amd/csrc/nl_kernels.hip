@@ -19,37 +19,9 @@
 #include <hip/hip_runtime.h>
 
 #include "cdfem_internal.hpp"
+#include "point_geom.hpp"
 
 namespace cdfem {
-
-// adj(J) (A[a][k] = det J d xi_a / d x_k) and det J of the affine map of element vertices V
-template <int DIM>
-__device__ __forceinline__ double simplex_adj(const double *__restrict__ V, double (&A)[DIM][DIM])
-{
-    double J[DIM][DIM];
-#pragma unroll
-    for (int k = 0; k < DIM; ++k)
-#pragma unroll
-        for (int m = 0; m < DIM; ++m) J[k][m] = V[(m + 1) * DIM + k] - V[k];
-    if constexpr (DIM == 3) {
-        A[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-        A[0][1] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
-        A[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
-        A[1][0] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-        A[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
-        A[1][2] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
-        A[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-        A[2][1] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
-        A[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-        return J[0][0] * A[0][0] + J[0][1] * A[1][0] + J[0][2] * A[2][0];
-    } else {
-        A[0][0] = J[1][1];
-        A[0][1] = -J[0][1];
-        A[1][0] = -J[1][0];
-        A[1][1] = J[0][0];
-        return J[0][0] * J[1][1] - J[0][1] * J[1][0];
-    }
-}
 
 template <int DIM, int P>
 constexpr int simplex_nd() { return P == 1 ? DIM + 1 : P == 2 ? (DIM + 1) * (DIM + 2) / 2 : 10; }
@@ -86,21 +58,7 @@ __device__ __forceinline__ void nl_point(const double *__restrict__ phi, const d
 #pragma unroll
         for (int k = 0; k < DIM; ++k) gr[k] += dphi[i * DIM + k] * (ue[i] - ue[0]);
     }
-    double gk[DIM];
-#pragma unroll
-    for (int k = 0; k < DIM; ++k) {
-        gk[k] = 0.0;
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) gk[k] += A[a][k] * gr[a];
-    }
-    const double f = W / det;
-#pragma unroll
-    for (int b = 0; b < DIM; ++b) {
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) s += A[b][k] * gk[k];
-        t[b] = f * s;
-    }
+    metric_flux<DIM>(A, W / det, gr, t);
 }
 
 template <int DIM, int P>
@@ -113,7 +71,7 @@ k_nl_residual(const double *__restrict__ verts, const int32_t *__restrict__ edof
     const int e = blockIdx.x * 64 + threadIdx.x;
     if (e >= ne) return;
     double A[DIM][DIM];
-    const double det = simplex_adj<DIM>(verts + (size_t)e * (DIM + 1) * DIM, A);
+    const double det = simplex_adjugate<DIM>(verts + (size_t)e * (DIM + 1) * DIM, A);
     double ue[ND], de[ND], r[ND];
     nl_gather<ND>(edofs + (size_t)e * ND, u, uold, ue, de);
 #pragma unroll
@@ -148,7 +106,7 @@ k_nl_gradient(const double *__restrict__ verts, const int32_t *__restrict__ edof
     const int e = blockIdx.x * 64 + threadIdx.x;
     if (e >= ne) return;
     double A[DIM][DIM];
-    const double det = simplex_adj<DIM>(verts + (size_t)e * (DIM + 1) * DIM, A);
+    const double det = simplex_adjugate<DIM>(verts + (size_t)e * (DIM + 1) * DIM, A);
     double ue[ND], de[ND];
     nl_gather<ND>(edofs + (size_t)e * ND, u, uold, ue, de);
     double M[ND][ND];
@@ -279,11 +237,6 @@ k_bdr_gather(const int32_t *__restrict__ off, const int32_t *__restrict__ pos, c
 }
 
 // ---- launchers ---------------------------------------------------------------------------------
-static cdfem_nl_heat_coeffs nl_coeffs(const cdfem_ctx *c)
-{
-    return cdfem_nl_heat_coeffs{c->heat.dt, c->heat.a0, c->heat.a1, c->heat.m0, c->heat.m1, c->heat.u_ref};
-}
-
 hipError_t launch_nl_residual(cdfem_ctx *c, const double *u, double *Ye)
 {
     const dim3 g((c->ne + 63) / 64), b(64);

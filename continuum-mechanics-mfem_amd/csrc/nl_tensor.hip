@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cdfem_internal.hpp"
+#include "point_geom.hpp"
 
 namespace cdfem {
 
@@ -39,73 +40,24 @@ struct NlTab {
 };
 
 template <int DIM, int P>
-struct NlShape {
-    static constexpr int D1 = P + 1;
-    static constexpr int Q1 = DIM == 3 ? P + 3 : P + 2;
-    static constexpr int D1Z = DIM == 3 ? D1 : 1;
-    static constexpr int Q1Z = DIM == 3 ? Q1 : 1;
-    static constexpr int ND = D1 * D1 * D1Z;
-    static constexpr int NV = 1 << DIM;
+struct NlShape : TensorShape<DIM, P, nl_tensor_points_1d(DIM, P)> {
+    using TensorShape<DIM, P, nl_tensor_points_1d(DIM, P)>::Q1;
     static constexpr int TPE = Q1 * Q1;     // threads per element
     static constexpr int EPB = 256 / TPE;   // elements per workgroup
     static constexpr int NT = EPB * TPE;    // live threads of the workgroup
 };
 
-// adj(J) (A[a][k] = det J d xi_a / d x_k) and det J; J[k][m] = d x_k / d xi_m
-template <int DIM>
-__device__ __forceinline__ double nl_adj(const double (&J)[DIM][DIM], double (&A)[DIM][DIM])
-{
-    if constexpr (DIM == 3) {
-        A[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-        A[0][1] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
-        A[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
-        A[1][0] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-        A[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
-        A[1][2] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
-        A[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-        A[2][1] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
-        A[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-        return J[0][0] * A[0][0] + J[0][1] * A[1][0] + J[0][2] * A[2][0];
-    } else {
-        A[0][0] = J[1][1];
-        A[0][1] = -J[0][1];
-        A[1][0] = -J[1][0];
-        A[1][1] = J[0][0];
-        return J[0][0] * J[1][1] - J[0][1] * J[1][0];
-    }
-}
-
-// t[b] = f sum_k A[b][k] (sum_a A[a][k] g[a]): f adj(J) adj(J)^T applied to a reference gradient
-template <int DIM>
-__device__ __forceinline__ void nl_flux(const double (&A)[DIM][DIM], double f, const double (&g)[DIM], double (&t)[DIM])
-{
-    double gk[DIM];
-#pragma unroll
-    for (int k = 0; k < DIM; ++k) {
-        gk[k] = 0.0;
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) gk[k] += A[a][k] * g[a];
-    }
-#pragma unroll
-    for (int b = 0; b < DIM; ++b) {
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) s += A[b][k] * gk[k];
-        t[b] = f * s;
-    }
-}
-
 // slots: the element slots of the context's layout (64 per block; perm[slot] = element, -1 = padding)
 template <int DIM, int P, int MODE>
 __global__ void __launch_bounds__(256)
 k_nl_tensor(const int32_t *__restrict__ map, const int32_t *__restrict__ perm, const double *__restrict__ verts,
-            int nslots, const NlTab<P + 1, (DIM == 3 ? P + 3 : P + 2)> T, cdfem_nl_heat_coeffs k,
+            int nslots, const NlTab<P + 1, nl_tensor_points_1d(DIM, P)> T, cdfem_nl_heat_coeffs k,
             const double *__restrict__ u, const double *__restrict__ uold, const double *__restrict__ v, int con,
             double *__restrict__ Ye, const KrylovState *__restrict__ st)
 {
     if (st != nullptr && st->done) return;
     using S = NlShape<DIM, P>;
-    constexpr int D1 = S::D1, Q1 = S::Q1, D1Z = S::D1Z, Q1Z = S::Q1Z, ND = S::ND, NV = S::NV, TPE = S::TPE,
+    constexpr int D1 = S::D1, Q1 = S::Q1, D1Z = S::DZ, Q1Z = S::QZ, ND = S::ND, NV = S::NV, TPE = S::TPE,
                   EPB = S::EPB, NT = S::NT;
     constexpr int NP = MODE == kNlDiag ? 6 : 3;   // accumulators per dz
     constexpr int NF = MODE == kNlJvp ? 3 : 2;    // fields in LDS: u, u - u_old, v
@@ -274,10 +226,10 @@ k_nl_tensor(const int32_t *__restrict__ map, const int32_t *__restrict__ perm, c
                     J[i][1] = Jy[0][i];
                 }
             }
-            const double det = nl_adj<DIM>(J, A);
+            const double det = adjugate<DIM>(J, A);
             const double au = k.a0 + k.a1 * (uq - k.u_ref), mu = k.m0 + k.m1 * (uq - k.u_ref);
             double tu[DIM];
-            nl_flux<DIM>(A, W / det, gu, tu);
+            metric_flux<DIM>(A, W / det, gu, tu);
             if constexpr (MODE != kNlDiag) {
                 double s, fl[DIM];
                 if constexpr (MODE == kNlResidual) {
@@ -286,7 +238,7 @@ k_nl_tensor(const int32_t *__restrict__ map, const int32_t *__restrict__ perm, c
                     for (int b = 0; b < DIM; ++b) fl[b] = au * tu[b];
                 } else {
                     double tv[DIM];
-                    nl_flux<DIM>(A, W / det, gv, tv);
+                    metric_flux<DIM>(A, W / det, gv, tv);
                     s = W * det * (mu + k.m1 * dq) * idt * vq;
 #pragma unroll
                     for (int b = 0; b < DIM; ++b) fl[b] = au * tv[b] + (k.a1 * vq) * tu[b];
@@ -369,9 +321,9 @@ k_nl_tensor(const int32_t *__restrict__ map, const int32_t *__restrict__ perm, c
 
 // ---- launchers -----------------------------------------------------------------------------------
 template <int DIM, int P>
-static NlTab<P + 1, (DIM == 3 ? P + 3 : P + 2)> nl_tab(const Rule1D &r)
+static NlTab<P + 1, nl_tensor_points_1d(DIM, P)> nl_tab(const Rule1D &r)
 {
-    NlTab<P + 1, (DIM == 3 ? P + 3 : P + 2)> t;
+    NlTab<P + 1, nl_tensor_points_1d(DIM, P)> t;
     for (int q = 0; q < r.q1; ++q) {
         for (int d = 0; d < r.d1; ++d) {
             t.B[q][d] = r.B[q][d];
@@ -384,18 +336,16 @@ static NlTab<P + 1, (DIM == 3 ? P + 3 : P + 2)> nl_tab(const Rule1D &r)
 }
 
 bool nl_tensor_supported(int dim, int p) { return dim == 2 ? (p >= 1 && p <= 3) : dim == 3 ? (p == 1 || p == 2) : false; }
-int nl_tensor_points_1d(int dim, int p) { return dim == 3 ? p + 3 : p + 2; }
 
 // mode: 0 residual (Ye = the elements' shares of R at u), 1 jvp (of J(u) v), 2 diagonal (of J(u)'s diagonal)
 hipError_t launch_nl_tensor(cdfem_ctx *c, int mode, const double *u, const double *v, bool con, double *Ye,
                             const KrylovState *st)
 {
-    if (!nl_tensor_supported(c->dim, c->p)) return hipErrorInvalidValue;
     const NlState &H = c->heat;
-    const cdfem_nl_heat_coeffs k{H.dt, H.a0, H.a1, H.m0, H.m1, H.u_ref};
+    const cdfem_nl_heat_coeffs k = nl_coeffs(c);
     const int nslots = c->nblk * kLanes;
-    return dispatch_value<21, 22, 23, 31, 32>(10 * c->dim + c->p, hipErrorInvalidValue, [&](auto DP) {
-        constexpr int DIM = DP() / 10, P = DP() % 10;
+    return dispatch_nl_tensor(c, [&](auto D, auto Pc) {
+        constexpr int DIM = D(), P = Pc();
         const auto T = nl_tab<DIM, P>(H.rule);
         const dim3 grid((unsigned)((nslots + NlShape<DIM, P>::EPB - 1) / NlShape<DIM, P>::EPB)), block(256);
         return dispatch_value<0, 1, 2>(mode, hipErrorInvalidValue, [&](auto M) {

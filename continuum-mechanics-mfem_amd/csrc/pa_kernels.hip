@@ -17,6 +17,7 @@
 #include "cdfem_internal.hpp"
 #include "dispatch.hpp"
 #include "pa_core.hpp"
+#include "point_geom.hpp"
 
 namespace cdfem {
 
@@ -171,73 +172,8 @@ k_apply2d(const int32_t *__restrict__ map, const double *__restrict__ x,
 }
 
 // ------------------------------------------------------------------------------------------------
-// geometry helpers (multilinear map, lexicographic vertices)
+// setup kernels (the multilinear map, its adjugate and the rule's points: point_geom.hpp)
 // ------------------------------------------------------------------------------------------------
-template <int DIM>
-__device__ inline void q1_map(const double *__restrict__ V, const double xi[3], double x[3],
-                              double J[3][3])
-{
-    constexpr int NV = 1 << DIM;
-    for (int i = 0; i < DIM; ++i) {
-        x[i] = 0.0;
-        for (int k = 0; k < DIM; ++k) J[i][k] = 0.0;
-    }
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        double f[3], df[3];
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) {
-            const int bit = (v >> k) & 1;
-            f[k] = bit ? xi[k] : 1.0 - xi[k];
-            df[k] = bit ? 1.0 : -1.0;
-        }
-        double N = 1.0;
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) N *= f[k];
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) {
-            double dN = df[k];
-#pragma unroll
-            for (int m = 0; m < DIM; ++m)
-                if (m != k) dN *= f[m];
-#pragma unroll
-            for (int i = 0; i < DIM; ++i) J[i][k] += V[v * DIM + i] * dN;
-        }
-#pragma unroll
-        for (int i = 0; i < DIM; ++i) x[i] += V[v * DIM + i] * N;
-    }
-}
-
-template <int DIM>
-__device__ inline double adjugate(const double J[3][3], double A[3][3])
-{
-    if constexpr (DIM == 2) {
-        A[0][0] = J[1][1]; A[0][1] = -J[0][1];
-        A[1][0] = -J[1][0]; A[1][1] = J[0][0];
-        return J[0][0] * J[1][1] - J[0][1] * J[1][0];
-    } else {
-        A[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-        A[0][1] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
-        A[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
-        A[1][0] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-        A[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
-        A[1][2] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
-        A[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-        A[2][1] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
-        A[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-        return J[0][0] * A[0][0] + J[0][1] * A[1][0] + J[0][2] * A[2][0];
-    }
-}
-
-__device__ inline void qpoint(int q, int q1, int dim, const Rule1D &r, double xi[3], double &W)
-{
-    const int qx = q % q1, qy = (q / q1) % q1, qz = q / (q1 * q1);
-    xi[0] = r.pts[qx];
-    xi[1] = r.pts[qy];
-    xi[2] = dim == 3 ? r.pts[qz] : 0.0;
-    W = r.wts[qx] * r.wts[qy] * (dim == 3 ? r.wts[qz] : 1.0);
-}
-
 // qdata setup: thread per (element-block, q, lane); coalesced writes of the [b][q][c][lane] layout
 template <int DIM>
 __global__ void __launch_bounds__(256)
@@ -277,9 +213,10 @@ k_setup_qdata(const double *__restrict__ verts, const int32_t *__restrict__ perm
             for (int k = 0; k < nc; ++k) gaff[((size_t)b * nc + k) * kLanes + lane] = 0.0;
         return;
     }
-    double xi[3], W;
-    qpoint(q, q1, DIM, r, xi, W);
-    double x[3], J[3][3], A[3][3];
+    int qi[3];
+    double xi[DIM], W;
+    tensor_point<DIM>(q, q1, r, qi, xi, W);
+    double J[DIM][DIM], A[DIM][DIM];
     const double *V = verts + (size_t)e * (1 << DIM) * DIM;
     if (gaff) {
         for (int i = 0; i < DIM; ++i)
@@ -306,7 +243,7 @@ k_setup_qdata(const double *__restrict__ verts, const int32_t *__restrict__ perm
         if (kinds & CDFEM_MASS) put_g(o++, W, mass * det);
         return;
     }
-    q1_map<DIM>(V, xi, x, J);
+    multilinear_map<DIM>(V, xi, J);
     const double det = adjugate<DIM>(J, A);
     const size_t eq = (size_t)e * nq + q;
     int o = 0;
@@ -421,9 +358,10 @@ __global__ void k_quad_points(const double *__restrict__ verts, int ne, const Ru
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (int64_t)ne * nq) return;
     const int e = (int)(t / nq), q = (int)(t % nq);
-    double xi[3], W, x[3], J[3][3];
-    qpoint(q, q1, DIM, r, xi, W);
-    q1_map<DIM>(verts + (size_t)e * (1 << DIM) * DIM, xi, x, J);
+    int qi[3];
+    double xi[DIM], W, x[DIM], J[DIM][DIM];
+    tensor_point<DIM>(q, q1, r, qi, xi, W);
+    multilinear_map<DIM>(verts + (size_t)e * (1 << DIM) * DIM, xi, J, x);
     for (int k = 0; k < DIM; ++k) xyz[t * DIM + k] = x[k];
 }
 
@@ -752,9 +690,10 @@ k_lf_elem(const double *__restrict__ verts, const int32_t *__restrict__ perm, in
     double acc = 0.0;
     if (e >= 0 && e < ne) {
         for (int q = 0; q < nq; ++q) {
-            double xi[3], W, x[3], J[3][3], A[3][3], phi, g[3];
-            qpoint(q, q1, DIM, r, xi, W);
-            q1_map<DIM>(verts + (size_t)e * (1 << DIM) * DIM, xi, x, J);
+            int qi[3];
+            double xi[DIM], W, J[DIM][DIM], A[DIM][DIM], phi, g[3];
+            tensor_point<DIM>(q, q1, r, qi, xi, W);
+            multilinear_map<DIM>(verts + (size_t)e * (1 << DIM) * DIM, xi, J);
             const double det = adjugate<DIM>(J, A);
             basis_at(l, q, DIM, r, phi, g);
             acc += W * det * fq[(size_t)e * nq + q] * phi;
